@@ -9,9 +9,22 @@ every rank reassembles the image (the north_star's framebuffer gather); with RCC
 gather of frame i runs on a communication stream while frame i+1 renders. Total work
 is fixed as N grows ("scaling": "strong").
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W]             # the plain run
+    python bench.py --full                                            # + everything below "full"
+    python bench.py --dump-outputs DIR                                # + DIR/frame.npy
     python bench.py --resolution 4096 --width 4096 --samples 16      # c5's frame
     torchrun --nproc-per-node N --master-addr 127.0.0.1 bench.py --gpus N ...
+
+A plain run does only what `value` needs: it loads and uploads the scene, renders W
+warm-up frames, times K frames and prints the line (metric, value, unit, ms_per_step,
+the ray counts and the per-phase GPU ms of the timed frames). --dump-outputs DIR also
+writes the frame the last timed step produced (rank 0's reassembled float32 RGBA image,
+what a caller of raytrace() receives) to DIR/frame.npy; a frame above 64 MB is written
+as a fixed, seeded sample of its rows. Scene, camera samples and parameters are fixed by
+the arguments, so two builds can be compared frame for frame. Everything else -- roofline,
+roofline_walks, frame_sha256 / frame_matches_n1, the end-to-end frames, the algorithmic
+yardstick's instrumented pass and the three cpu_baseline legs -- takes work of its own
+after the timed region and is reported only with --full.
 
 `python bench.py --gpus N` with N > 1 and no WORLD_SIZE in the environment launches
 its own N ranks (one process per GPU, RANK/LOCAL_RANK/WORLD_SIZE/MASTER_* set) before
@@ -23,6 +36,8 @@ value     the reference's ray count over all ranks (camera + shadow + reflection
           without a walk (the shadow cull); config.rays_traced_per_frame and
           config.Mrays_traced_per_s give the rays actually walked, config.shadow_rays_culled_per_frame
           the difference
+
+full (only with --full):
 roofline  the roofline kernel is the longest per-ray phase of this run's frame (the
           per-render lists phase, fixed work whatever a rank's share, is never picked;
           roofline_phase()): the closest hit k_primary_persist at c4. The walks are bound by
@@ -91,7 +106,14 @@ def parse():
     p.add_argument("--resolution", type=int, default=1080)
     p.add_argument("--width", type=int, default=0)
     p.add_argument("--samples", type=int, default=8, help="per axis: 8 -> 64 spp")
-    p.add_argument("--cpu-seconds", type=float, default=12.0, help="CPU baseline budget per leg (0 = skip)")
+    p.add_argument("--full", action="store_true",
+                   help="also report what takes work beyond the timed steps: roofline, frame digest, end-to-end "
+                        "frames, the algorithmic yardstick's counting pass and the CPU baselines")
+    p.add_argument("--dump-outputs", metavar="DIR", default="",
+                   help="write the frame of the last timed step to DIR/frame.npy (float32; a seeded sample of "
+                        "rows when the frame exceeds 64 MB)")
+    p.add_argument("--cpu-seconds", type=float, default=12.0,
+                   help="with --full: CPU baseline budget per leg (0 = skip)")
     p.add_argument("--traffic-json", default=str(ROOT / "profiles" / "pmc_traffic.json"))
     p.add_argument("--issue-json", default=str(ROOT / "profiles" / "issue_counters.json"))
     p.add_argument("--algorithm", default="wavefront", choices=("wavefront", "megakernel", "wavefront_lane"))
@@ -403,6 +425,29 @@ def frame_matches_n1(digest, key: str, path: Path = DIGESTS):
     return None if want is None else digest == want
 
 
+DUMP_LIMIT = 64 << 20  # bytes written by --dump-outputs, at most
+
+
+def dump_rows(n_rows: int, row_bytes: int, limit: int = DUMP_LIMIT):
+    """the rows --dump-outputs writes: all of them (None) when the frame fits in `limit`
+    bytes, else a fixed, seeded, sorted sample of as many rows as fit"""
+    if n_rows * row_bytes <= limit:
+        return None
+    keep = max(1, limit // row_bytes)
+    return np.sort(np.random.default_rng(0).choice(n_rows, size=keep, replace=False))
+
+
+def dump_outputs(out_dir: str, frame) -> None:
+    """DIR/frame.npy: the float32 image (rows, W, 4) the timed path left on the device"""
+    rows = dump_rows(frame.shape[0], frame.shape[1] * frame.shape[2] * 4)
+    if rows is not None:
+        import torch
+
+        frame = frame[torch.as_tensor(rows, device=frame.device)]
+    Path(out_dir).mkdir(parents=True, exist_ok=True)
+    np.save(Path(out_dir) / "frame.npy", frame.detach().contiguous().cpu().numpy().astype(np.float32, copy=False))
+
+
 def main():
     a = parse()
     if "WORLD_SIZE" not in os.environ and a.gpus > 1:
@@ -510,61 +555,66 @@ def main():
         dist.barrier()
     torch.cuda.synchronize(dev)
     t0 = time.perf_counter()
+    b = 0
     for i in range(a.steps):
         # HIP events around every kernel launch, on the launch stream (library-side)
-        step(i, timing=1 if i == 0 else 2)
+        b = step(i, timing=1 if i == 0 else 2)
     torch.cuda.synchronize(dev)  # every stream of the device: renders and gathers
     if world > 1:
         dist.barrier()
     elapsed = time.perf_counter() - t0
     st = ds.last_stats()
     phases = ds.last_timings()  # {phase: (ms over the K steps, launches)}
-    try:
-        identity = code_identity(yrt_native.LIB_PATH)
-    except (OSError, ValueError, subprocess.CalledProcessError) as e:  # no binutils/bundler: no roofline
-        identity = f"unavailable ({type(e).__name__})"
-    dom = roofline_phase(phases, n1_ranking(Path(a.issue_json), f"{a.scene}-{W}x{H}-s{a.samples}-n1-{a.algorithm}-",
-                                            identity))
-    dom_ms = phases[dom][0] / a.steps  # per frame
-    dom_launches = phases[dom][1] / a.steps
     render_ms = sum(v[0] for v in phases.values()) / a.steps
+    if a.dump_outputs and rank == 0:
+        # the last timed step's frame (a --profile-rank run gathers nothing: its own bands)
+        dump_outputs(a.dump_outputs, shards[b] if a.profile_rank else frames[b])
 
-    # ---- end to end (untimed above): render + gather + the float frame to host memory
-    # (what raytrace() returns, image4f) + the device tonemap of save_hdr_or_ldr's PNG
-    e2e_frames = max(1, min(a.steps, 3))
-    host_frame = torch.empty((H, W, 4), dtype=torch.float32, pin_memory=True) if rank == 0 else None
-    ldr = torch.empty((H, W, 4), dtype=torch.uint8, device=dev) if rank == 0 else None
-    if world > 1:
-        dist.barrier()
-    torch.cuda.synchronize(dev)
-    t1 = time.perf_counter()
-    for i in range(e2e_frames):
-        b = step(a.steps + i)
-        if rank == 0:
-            if overlap:
-                stream.wait_event(gathered_ev[b])
-            yrt.tonemap_device(frames[b].data_ptr(), H * W, ldr.data_ptr(), stream=stream.cuda_stream)
-            host_frame.copy_(frames[b], non_blocking=True)
-            torch.cuda.synchronize(dev)
-    torch.cuda.synchronize(dev)
-    if world > 1:
-        dist.barrier()
-    e2e_ms = (time.perf_counter() - t1) / e2e_frames * 1e3
-    # rank 0's reassembled float frame (every step renders the same frame): an N-rank
-    # line can be checked bit for bit against the N = 1 line
-    frame_sha256 = None
-    if rank == 0 and not a.profile_rank:
-        frame_sha256 = frame_digest(frames[b])
+    dom, dom_ms, dom_launches, e2e_ms, frame_sha256, algo_bytes = None, 0.0, 0.0, 0.0, None, 0.0
+    if a.full:
+        try:
+            identity = code_identity(yrt_native.LIB_PATH)
+        except (OSError, ValueError, subprocess.CalledProcessError) as e:  # no binutils/bundler: no roofline
+            identity = f"unavailable ({type(e).__name__})"
+        dom = roofline_phase(phases, n1_ranking(Path(a.issue_json),
+                                                f"{a.scene}-{W}x{H}-s{a.samples}-n1-{a.algorithm}-", identity))
+        dom_ms = phases[dom][0] / a.steps  # per frame
+        dom_launches = phases[dom][1] / a.steps
 
-    # SURVEY §8(d)'s algorithmic yardstick, from one instrumented (untimed) pass of this
-    # rank's share: the reference's work counts x the reference layout's bytes per unit
-    algo_bytes = 0.0
-    if not a.no_count_pass:
-        params.count_work, params.timing = 1, 0
-        ds.render_into(params, shards[0].data_ptr(), stream=stream.cuda_stream)
+        # ---- end to end (untimed above): render + gather + the float frame to host memory
+        # (what raytrace() returns, image4f) + the device tonemap of save_hdr_or_ldr's PNG
+        e2e_frames = max(1, min(a.steps, 3))
+        host_frame = torch.empty((H, W, 4), dtype=torch.float32, pin_memory=True) if rank == 0 else None
+        ldr = torch.empty((H, W, 4), dtype=torch.uint8, device=dev) if rank == 0 else None
+        if world > 1:
+            dist.barrier()
         torch.cuda.synchronize(dev)
-        algo_bytes = algorithmic_bytes(ds.last_stats(), local_rows * W)
-        params.count_work = 0
+        t1 = time.perf_counter()
+        for i in range(e2e_frames):
+            b = step(a.steps + i)
+            if rank == 0:
+                if overlap:
+                    stream.wait_event(gathered_ev[b])
+                yrt.tonemap_device(frames[b].data_ptr(), H * W, ldr.data_ptr(), stream=stream.cuda_stream)
+                host_frame.copy_(frames[b], non_blocking=True)
+                torch.cuda.synchronize(dev)
+        torch.cuda.synchronize(dev)
+        if world > 1:
+            dist.barrier()
+        e2e_ms = (time.perf_counter() - t1) / e2e_frames * 1e3
+        # rank 0's reassembled float frame (every step renders the same frame): an N-rank
+        # line can be checked bit for bit against the N = 1 line
+        if rank == 0 and not a.profile_rank:
+            frame_sha256 = frame_digest(frames[b])
+
+        # SURVEY §8(d)'s algorithmic yardstick, from one instrumented (untimed) pass of this
+        # rank's share: the reference's work counts x the reference layout's bytes per unit
+        if not a.no_count_pass:
+            params.count_work, params.timing = 1, 0
+            ds.render_into(params, shards[0].data_ptr(), stream=stream.cuda_stream)
+            torch.cuda.synchronize(dev)
+            algo_bytes = algorithmic_bytes(ds.last_stats(), local_rows * W)
+            params.count_work = 0
 
     t = torch.tensor([elapsed, dom_ms, render_ms, e2e_ms], dtype=torch.float64, device=dev)
     rays = torch.tensor([st["rays"] * a.steps, st["camera_samples"] * a.steps, algo_bytes,
@@ -580,43 +630,6 @@ def main():
         spp = a.samples * a.samples
         is_c4 = (a.scene, a.resolution, a.width, a.samples) == ("instance10000", 1080, 0, 8)
         metric = BASELINE_METRIC if is_c4 else f"Mrays/sec + ms/frame, {a.scene} {W}×{H}×{spp}spp, {world} MI355X"
-        key = f"{a.scene}-{W}x{H}-s{a.samples}-n{band_world}-{a.algorithm}-{dom}"
-        kernel_ms = dom_ms / dom_launches
-        tr, _ = load_counters(Path(a.traffic_json), key, identity)
-        traffic = tr.get("hbm_bytes_per_launch") if tr else None
-        key_n1 = f"{a.scene}-{W}x{H}-s{a.samples}-n1-{a.algorithm}-{dom}"
-        share = (st["rays"] * a.steps) / total_rays if total_rays else 1.0  # rank 0's share of the frame
-        bound, pipes, rec = issue_roofline(Path(a.issue_json), key, kernel_ms, identity, key_n1, share)
-        # both walks' issue rooflines (the closest hit and the any hit), whichever is longer
-        walks = {}
-        for ph in ("primary", "shadow"):
-            if ph not in phases or not phases[ph][1]:
-                continue
-            ph_ms = phases[ph][0] / phases[ph][1]
-            wb, wp, wr = issue_roofline(Path(a.issue_json), f"{a.scene}-{W}x{H}-s{a.samples}-n{band_world}-"
-                                        f"{a.algorithm}-{ph}", ph_ms, identity,
-                                        f"{a.scene}-{W}x{H}-s{a.samples}-n1-{a.algorithm}-{ph}", share)
-            walks[ph] = ({"kernel": wr.get("kernel", PHASE_KERNEL.get(ph, ph)), "kernel_ms": ph_ms, "bound": wb,
-                          "frac": wp[wb]["frac"], "salu_frac": wp["salu"]["frac"], "valu_frac": wp["valu"]["frac"]}
-                         if wb else {"kernel": PHASE_KERNEL.get(ph, ph), "kernel_ms": ph_ms, "frac": None,
-                                     "note": wr})
-        if bound:
-            roof = {"bound": "issue", "pipe": bound, "achieved": pipes[bound]["achieved"],
-                    "peak": pipes[bound]["peak"], "unit": "G wave-instructions/s", "frac": pipes[bound]["frac"],
-                    "traffic": traffic, "kernel": rec.get("kernel", PHASE_KERNEL.get(dom, dom)), "kernel_ms": kernel_ms,
-                    "pipes": pipes, "counters": rec.get("source"),
-                    "code_identity": identity,
-                    "hbm": {"bytes_per_launch": traffic,
-                            "achieved_GBs": traffic / (kernel_ms / 1e3) / 1e9 if traffic else None,
-                            "peak_GBs": HBM_PEAK_GBS,
-                            "frac": traffic / (kernel_ms / 1e3) / 1e9 / HBM_PEAK_GBS if traffic else None},
-                    "note": ("SQ_INSTS_* per launch from the committed rocprofv3 counters of this exact "
-                             "configuration / live HIP-event launch time; peak at the 2.4 GHz max clock")}
-        else:
-            roof = {"bound": "issue", "achieved": None, "peak": None, "unit": "G wave-instructions/s",
-                    "frac": None, "traffic": traffic, "kernel": PHASE_KERNEL.get(dom, dom),
-                    "kernel_ms": kernel_ms, "code_identity": identity,
-                    "note": f"{rec} (tools/gpu/issue_pmc.sh collects them)"}
         line = {
             "metric": metric,
             "value": total_rays / elapsed / 1e6,
@@ -644,35 +657,76 @@ def main():
                                      "term is exactly zero, answered without a walk (identical image)"),
                        "camera_samples_per_frame": total_samples / a.steps,
                        "gpu_ms_per_frame": render_ms,
-                       "ms_per_frame_end_to_end": e2e_ms,
-                       "end_to_end": "render + gather + float frame to pinned host memory + device tonemap",
                        "phase_ms_per_frame": {k: v[0] / a.steps for k, v in phases.items()},
                        "camera_Msamples_per_s": total_samples / elapsed / 1e6,
                        "algorithm": a.algorithm},
-            "roofline": roof,
-            "algorithmic_yardstick": None if a.no_count_pass else {
-                "bytes_per_frame": total_algo_bytes,
-                "GBs": total_algo_bytes / (elapsed / a.steps) / 1e9,
-                "frac_of_hbm_peak": total_algo_bytes / (elapsed / a.steps) / 1e9 / HBM_PEAK_GBS / world,
-                "note": ("SURVEY §8(d): 32 B per box test, 56 B per instance entry, 52 B per primitive test, "
-                         "216 B per shaded hit, 16 B per texture lookup, 16 B per pixel, with the reference's "
-                         "own work counts (one instrumented pass, untimed), over the timed ms/frame. The "
-                         "reference's per-ray fetches of its AoS layout, not this path's traffic: the packet "
-                         "walks fetch each record once per 64-ray wave from a cache-resident scene, so this "
-                         "exceeds the HBM peak; roofline above is the bound that applies.")},
-            "roofline_walks": walks,
-            "frame_sha256": frame_sha256,
-            "frame_matches_n1": frame_matches_n1(frame_sha256, digest_key(a.scene, W, H, a.samples)),
         }
         if a.profile_rank:  # a counter-collection run, not a bench result
             line["metric"] = f"profile of rank {a.profile_rank} (bands only, no gather): {metric}"
             line["config"]["parallelism"] = f"rank {a.profile_rank} of an image-band split, rendered alone"
-        if world == 1 and a.cpu_seconds > 0 and not a.profile_rank:
-            line["cpu_baseline"] = cpu_baseline(scene_file, a.resolution, a.width, a.samples, a.cpu_seconds)
-            line["cpu_baseline_all_cores"] = cpu_baseline_all_cores(scene_file, a.resolution, a.width, a.samples,
-                                                                    a.cpu_seconds)
-            line["cpu_baseline_port_all_cores"] = cpu_baseline_port_all_cores(scene_file, a.resolution, a.width,
-                                                                              a.samples, a.cpu_seconds)
+        if a.full:
+            key = f"{a.scene}-{W}x{H}-s{a.samples}-n{band_world}-{a.algorithm}-{dom}"
+            kernel_ms = dom_ms / dom_launches
+            tr, _ = load_counters(Path(a.traffic_json), key, identity)
+            traffic = tr.get("hbm_bytes_per_launch") if tr else None
+            key_n1 = f"{a.scene}-{W}x{H}-s{a.samples}-n1-{a.algorithm}-{dom}"
+            share = (st["rays"] * a.steps) / total_rays if total_rays else 1.0  # rank 0's share of the frame
+            bound, pipes, rec = issue_roofline(Path(a.issue_json), key, kernel_ms, identity, key_n1, share)
+            # both walks' issue rooflines (the closest hit and the any hit), whichever is longer
+            walks = {}
+            for ph in ("primary", "shadow"):
+                if ph not in phases or not phases[ph][1]:
+                    continue
+                ph_ms = phases[ph][0] / phases[ph][1]
+                wb, wp, wr = issue_roofline(Path(a.issue_json), f"{a.scene}-{W}x{H}-s{a.samples}-n{band_world}-"
+                                            f"{a.algorithm}-{ph}", ph_ms, identity,
+                                            f"{a.scene}-{W}x{H}-s{a.samples}-n1-{a.algorithm}-{ph}", share)
+                walks[ph] = ({"kernel": wr.get("kernel", PHASE_KERNEL.get(ph, ph)), "kernel_ms": ph_ms, "bound": wb,
+                              "frac": wp[wb]["frac"], "salu_frac": wp["salu"]["frac"], "valu_frac": wp["valu"]["frac"]}
+                             if wb else {"kernel": PHASE_KERNEL.get(ph, ph), "kernel_ms": ph_ms, "frac": None,
+                                         "note": wr})
+            if bound:
+                roof = {"bound": "issue", "pipe": bound, "achieved": pipes[bound]["achieved"],
+                        "peak": pipes[bound]["peak"], "unit": "G wave-instructions/s", "frac": pipes[bound]["frac"],
+                        "traffic": traffic, "kernel": rec.get("kernel", PHASE_KERNEL.get(dom, dom)), "kernel_ms": kernel_ms,
+                        "pipes": pipes, "counters": rec.get("source"),
+                        "code_identity": identity,
+                        "hbm": {"bytes_per_launch": traffic,
+                                "achieved_GBs": traffic / (kernel_ms / 1e3) / 1e9 if traffic else None,
+                                "peak_GBs": HBM_PEAK_GBS,
+                                "frac": traffic / (kernel_ms / 1e3) / 1e9 / HBM_PEAK_GBS if traffic else None},
+                        "note": ("SQ_INSTS_* per launch from the committed rocprofv3 counters of this exact "
+                                 "configuration / live HIP-event launch time; peak at the 2.4 GHz max clock")}
+            else:
+                roof = {"bound": "issue", "achieved": None, "peak": None, "unit": "G wave-instructions/s",
+                        "frac": None, "traffic": traffic, "kernel": PHASE_KERNEL.get(dom, dom),
+                        "kernel_ms": kernel_ms, "code_identity": identity,
+                        "note": f"{rec} (tools/gpu/issue_pmc.sh collects them)"}
+            line["config"].update({
+                "ms_per_frame_end_to_end": e2e_ms,
+                "end_to_end": "render + gather + float frame to pinned host memory + device tonemap"})
+            line.update({
+                "roofline": roof,
+                "algorithmic_yardstick": None if a.no_count_pass else {
+                    "bytes_per_frame": total_algo_bytes,
+                    "GBs": total_algo_bytes / (elapsed / a.steps) / 1e9,
+                    "frac_of_hbm_peak": total_algo_bytes / (elapsed / a.steps) / 1e9 / HBM_PEAK_GBS / world,
+                    "note": ("SURVEY §8(d): 32 B per box test, 56 B per instance entry, 52 B per primitive test, "
+                             "216 B per shaded hit, 16 B per texture lookup, 16 B per pixel, with the reference's "
+                             "own work counts (one instrumented pass, untimed), over the timed ms/frame. The "
+                             "reference's per-ray fetches of its AoS layout, not this path's traffic: the packet "
+                             "walks fetch each record once per 64-ray wave from a cache-resident scene, so this "
+                             "exceeds the HBM peak; roofline above is the bound that applies.")},
+                "roofline_walks": walks,
+                "frame_sha256": frame_sha256,
+                "frame_matches_n1": frame_matches_n1(frame_sha256, digest_key(a.scene, W, H, a.samples)),
+            })
+            if world == 1 and a.cpu_seconds > 0 and not a.profile_rank:
+                line["cpu_baseline"] = cpu_baseline(scene_file, a.resolution, a.width, a.samples, a.cpu_seconds)
+                line["cpu_baseline_all_cores"] = cpu_baseline_all_cores(scene_file, a.resolution, a.width, a.samples,
+                                                                        a.cpu_seconds)
+                line["cpu_baseline_port_all_cores"] = cpu_baseline_port_all_cores(scene_file, a.resolution, a.width,
+                                                                                  a.samples, a.cpu_seconds)
         print(json.dumps(line), flush=True)
     if world > 1:
         dist.destroy_process_group()

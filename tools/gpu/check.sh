@@ -12,4 +12,4 @@ tail -n 3 $OUT/pytest.log
 if grep -q "illegal memory\|Aborted\|Segmentation\|Timeout" $OUT/pytest.log || [ $rc -ge 124 ]; then
   exit 1
 fi
-timeout -k 10 300 python bench.py --cpu-seconds 0 "$@" > $OUT/bench.json 2> $OUT/bench.err
+timeout -k 10 300 python bench.py --full --cpu-seconds 0 "$@" > $OUT/bench.json 2> $OUT/bench.err

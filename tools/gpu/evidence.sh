@@ -32,18 +32,18 @@ if [ "$PART" = A ]; then
   run timeout -k 10 120 python -c "import __graft_entry__ as g; g.smoke()" > $OUT/smoke.log 2>&1
   pmc pmc_c4 150
   summ instance10000-1920x1080-s8-n1-wavefront $OUT/pmc_c4
-  run timeout -k 10 400 python bench.py > $OUT/bench.json 2> $OUT/bench.err
+  run timeout -k 10 400 python bench.py --full > $OUT/bench.json 2> $OUT/bench.err
   cut -c1-300 $OUT/bench.json
   YRT_BENCH_DEVICES=1 YRT_BENCH_BACKEND=gloo YRT_BENCH_OVERLAP=1 run timeout -k 10 400 \
-    python bench.py --gpus 2 --steps 3 --warmup 1 --cpu-seconds 0 > $OUT/bench_n2_rehearsal_gloo_1gpu.json 2> $OUT/n2.err
+    python bench.py --full --gpus 2 --steps 3 --warmup 1 --cpu-seconds 0 > $OUT/bench_n2_rehearsal_gloo_1gpu.json 2> $OUT/n2.err
   grep -h '^{' $OUT/bench_n2_rehearsal_gloo_1gpu.json | cut -c1-300
 elif [ "$PART" = B ]; then
   pmc pmc_c3 200 --scene refl --resolution 1080 --samples 4
   summ refl-1920x1080-s4-n1-wavefront $OUT/pmc_c3
   pmc pmc_c5 300 --resolution 4096 --width 4096 --samples 16
   summ instance10000-4096x4096-s16-n1-wavefront $OUT/pmc_c5
-  run timeout -k 10 300 python bench.py --scene refl --resolution 1080 --samples 4 --cpu-seconds 0 > $OUT/bench_c3_refl.json 2> $OUT/c3.err
-  run timeout -k 10 400 python bench.py --resolution 4096 --width 4096 --samples 16 --steps 2 --warmup 1 --cpu-seconds 6 > $OUT/bench_c5_1gpu.json 2> $OUT/c5.err
+  run timeout -k 10 300 python bench.py --full --scene refl --resolution 1080 --samples 4 --cpu-seconds 0 > $OUT/bench_c3_refl.json 2> $OUT/c3.err
+  run timeout -k 10 400 python bench.py --full --resolution 4096 --width 4096 --samples 16 --steps 2 --warmup 1 --cpu-seconds 6 > $OUT/bench_c5_1gpu.json 2> $OUT/c5.err
   cut -c1-300 $OUT/bench_c3_refl.json $OUT/bench_c5_1gpu.json
 elif [ "$PART" = C ]; then
   run timeout -k 10 300 python tools/rank_share.py > $OUT/rank_share_c4.json 2> $OUT/rank_share.err
@@ -60,7 +60,7 @@ else
   for s in instance1k instance100k; do
     pmc pmc_$s 200 --scene $s
     summ $s-1920x1080-s8-n1-wavefront $OUT/pmc_$s
-    run timeout -k 10 300 python bench.py --scene $s --cpu-seconds 0 > $OUT/bench_$s.json 2> $OUT/$s.err
+    run timeout -k 10 300 python bench.py --full --scene $s --cpu-seconds 0 > $OUT/bench_$s.json 2> $OUT/$s.err
     cut -c1-300 $OUT/bench_$s.json
   done
 fi

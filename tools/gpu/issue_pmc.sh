@@ -9,7 +9,7 @@ TAG=$1; shift
 export TMPDIR=/tmp
 OUT=gpurun_out/$TAG
 mkdir -p $OUT
-B="bench.py --steps 1 --warmup 0 --cpu-seconds 0 --no-count-pass $*"
+B="bench.py --full --steps 1 --warmup 0 --cpu-seconds 0 --no-count-pass $*"
 groups=(
   "SQ_INSTS_SALU SQ_INSTS_VALU SQ_INSTS_SMEM SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES GRBM_GUI_ACTIVE"
   "SQ_WAIT_INST_ANY SQ_WAIT_ANY SQ_ACTIVE_INST_ANY SQ_INSTS_LDS SQ_INSTS_BRANCH GRBM_GUI_ACTIVE"
@@ -25,6 +25,6 @@ for g in "${groups[@]}"; do
   echo "pass $i ($g): rc=$rc"
   if [ $rc -ge 124 ]; then exit $rc; fi
 done
-timeout -k 10 200 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/ks -o ks -- python3 bench.py --steps 3 --warmup 1 --cpu-seconds 0 "$@" > $OUT/ks.log 2>&1
+timeout -k 10 200 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/ks -o ks -- python3 bench.py --full --steps 3 --warmup 1 --cpu-seconds 0 "$@" > $OUT/ks.log 2>&1
 echo "kernel stats: rc=$?"
 find $OUT -name '*.csv' | sort
