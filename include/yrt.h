@@ -268,6 +268,32 @@ int yrt_multi_last_timings(const yrt_multi* m, float* render_ms, float* gather_m
 int yrt_render_multi(const yrt_host_scene* hs, const int* devices, int n, const yrt_render_params* p, float* out,
                      int mem);
 
+/* ---- AOVs: the camera hit's geometry buffers ----
+ * A pass of its own over the beauty's sample grid and box filter (raytrace.cpp:228-250): per
+ * pixel the s*s camera samples, jj outer and ii inner, each answered by intersect_first. A
+ * float AOV is the float32 sum, in that order, of the value below over the samples that hit,
+ * divided by float(s*s); a miss adds nothing, so .xyz is premultiplied by .w, the coverage
+ * (hits / (s*s)) -- divide by .w to un-premultiply.
+ *   DEPTH     float4 {dist, 0, 0, w}  intersection3f::dist along the normalised camera ray
+ *   POSITION  float4 {eval_pos, w}    world position (scene.h:159-172)
+ *   NORMAL    float4 {eval_norm, w}   world shading normal, not renormalised after averaging
+ *   TEXCOORD  float4 {u, v, 0, w}     eval_texcoord; points give {0, 0}
+ *   ALBEDO    float4 {kd, w}          mat->kd, times its kd_txt lookup (raytrace.cpp:150-154)
+ *   IDS       int4, not averaged: the pixel's first sample (jj = 0, ii = 0) as {instance index
+ *             in scene order, ei, material index, shape index}; all -1 on a miss */
+enum { YRT_AOV_DEPTH = 0, YRT_AOV_POSITION = 1, YRT_AOV_NORMAL = 2, YRT_AOV_TEXCOORD = 3,
+       YRT_AOV_ALBEDO = 4, YRT_AOV_IDS = 5, YRT_AOV_COUNT = 6 };
+typedef struct yrt_aov_planes { void* plane[YRT_AOV_COUNT]; } yrt_aov_planes; /* 16 B per pixel each */
+/* mask: bit 1 << YRT_AOV_x per requested AOV; only their planes are read from `out` and
+ * written. Planes have the layout of yrt_render's output (row-major window, out_stride), and
+ * resolution, width, samples, camera, the window, the band interleave and out_stride of `p`
+ * mean what they mean there (local rows past the image edge read as zeros, ids -1); ambient,
+ * max_depth, algorithm, count_work and timing are ignored. `mem` and `stream` as in
+ * yrt_render: host planes make the call synchronous, device planes are stream-ordered.
+ * yrt_last_stats then reports rays == camera_samples == window pixels * s*s. */
+int yrt_render_aovs(yrt_scene* ds, const yrt_render_params* p, unsigned mask, const yrt_aov_planes* out, int mem,
+                    void* stream);
+
 #ifdef __cplusplus
 }
 #endif

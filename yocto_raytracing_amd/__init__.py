@@ -23,7 +23,7 @@ from . import _native as N
 from ._native import RenderParams, Stats, YrtError, check
 
 __all__ = [
-    "Scene", "DeviceScene", "load_scene", "build_bvh", "raytrace", "intersect_first",
+    "Scene", "DeviceScene", "load_scene", "build_bvh", "raytrace", "render_aovs", "intersect_first",
     "intersect_any", "tonemap", "save_hdr_or_ldr", "render_params", "device_count", "YrtError",
 ]
 
@@ -225,6 +225,17 @@ class DeviceScene:
         check(N.lib.yrt_render(self._h, C.byref(params), C.c_void_p(out_ptr), mem,
                                C.c_void_p(stream or 0)), "yrt_render")
 
+    def render_aovs_into(self, params: RenderParams, planes: dict, device_memory: bool = True,
+                         stream: Optional[int] = None) -> None:
+        """Launch the AOV pass (yrt_render_aovs) into caller planes {name: pointer}, 16 bytes
+        per pixel each in render_into's layout; only the named AOVs are computed."""
+        mask, ap = _aov_mask(planes), N.AovPlanes()
+        for name, ptr in planes.items():
+            ap.plane[N.AOVS[name]] = ptr
+        mem = N.YRT_MEM_DEVICE if device_memory else N.YRT_MEM_HOST
+        check(N.lib.yrt_render_aovs(self._h, C.byref(params), mask, C.byref(ap), mem, C.c_void_p(stream or 0)),
+              "yrt_render_aovs")
+
     def last_timings(self) -> dict:
         """per-phase GPU ms of the last render with timing=True: {phase: (ms, launches)}"""
         t = N.Timings()
@@ -371,6 +382,37 @@ def raytrace(scn, amb: Sequence[float] = (0.1, 0.1, 0.1), resolution: int = 720,
     if return_stats:
         return img, ds.last_stats()
     return img
+
+
+def _aov_mask(names) -> int:
+    """the YRT_AOV_* bit mask of AOV names; an unknown name raises before any native call"""
+    names = list(names)
+    bad = [n for n in names if n not in N.AOVS]
+    if bad or not names:
+        raise ValueError((f"unknown AOV {bad[0]!r}" if bad else "no AOV named") + f" (one of {', '.join(N.AOVS)})")
+    mask = 0
+    for n in names:
+        mask |= 1 << N.AOVS[n]
+    return mask
+
+
+def render_aovs(scn, resolution: int = 720, samples: int = 1, *, aovs: Sequence[str] = tuple(N.AOVS),
+                width: int = 0, camera: int = 0, window=None, device: int = 0) -> dict:
+    """The camera hit's geometry buffers on raytrace's sample grid: {name: (H, W, 4)}, float32
+    {value.xyz premultiplied by coverage, coverage} for "depth", "position", "normal",
+    "texcoord" and "albedo", int32 {instance, element, material, shape} of the pixel's first
+    sample for "ids" (-1 on a miss). `scn` is a Scene or a DeviceScene, as for raytrace."""
+    _aov_mask(aovs)
+    ds = _device_scene(scn, device)
+    p = render_params(resolution=resolution, samples=samples, width=width, camera=camera, window=window)
+    W, H = ds.image_size(p)
+    if window is None:
+        w, h = W, H
+    else:
+        w, h = window[2] or W - window[0], window[3] or H - window[1]
+    out = {n: np.zeros((h, w, 4), np.int32 if n == "ids" else np.float32) for n in aovs}
+    ds.render_aovs_into(p, {n: a.ctypes.data for n, a in out.items()}, device_memory=False)
+    return out
 
 
 def _rays_array(rays) -> np.ndarray:

@@ -88,6 +88,15 @@ class ShapeDesc(C.Structure):
                 ("lines", C.c_void_p), ("ntriangles", C.c_int), ("triangles", C.c_void_p)]
 
 
+# YRT_AOV_*: name -> plane index (bit of the mask); every plane is 16 bytes per pixel
+AOVS = {"depth": 0, "position": 1, "normal": 2, "texcoord": 3, "albedo": 4, "ids": 5}
+YRT_AOV_COUNT = 6
+
+
+class AovPlanes(C.Structure):
+    _fields_ = [("plane", C.c_void_p * YRT_AOV_COUNT)]
+
+
 _vp = C.c_void_p
 _ip = C.POINTER(C.c_int)
 _sig = {
@@ -135,6 +144,7 @@ _sig = {
     "yrt_multi_last_stats": (C.c_int, [_vp, C.POINTER(Stats)]),
     "yrt_multi_last_timings": (C.c_int, [_vp, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
     "yrt_render_multi": (C.c_int, [_vp, _ip, C.c_int, C.POINTER(RenderParams), _vp, C.c_int]),
+    "yrt_render_aovs": (C.c_int, [_vp, C.POINTER(RenderParams), C.c_uint, C.POINTER(AovPlanes), C.c_int, _vp]),
 }
 EXPORTS = tuple(_sig)
 

@@ -28,6 +28,9 @@ ARCH = os.environ.get("YRT_OFFLOAD_ARCH", "gfx950")
 
 SOURCES = ["obj_loader.cpp", "png.cpp", "scene_io.cpp", "bvh_build.cpp",
            "device_scene.cpp", "capi.cpp", "multi.cpp", "render.hip", "wavefront.hip", "bvh_gpu.hip"]
+# device sources that are part of another one's translation unit: render.hip ends by including
+# aov.hip (the AOV pass), so the library keeps one gfx950 code object per entry of SOURCES
+INCLUDED = {"render.hip": ["aov.hip"]}
 COMMON = ["-O3", "-fPIC", "-std=c++17", "-ffp-contract=off", "-Wall", "-Wno-unused-function",
           f"-I{CSRC}", f"-I{ROOT / 'include'}"]
 
@@ -85,7 +88,7 @@ def build_library(verbose: bool = False) -> Path:
             cmd = [HIPCC, *COMMON, *DEVICE_FLAGS, f"--offload-arch={ARCH}", "-c", str(s), "-o", str(o)]
         else:  # host-only C++: same clang, no offload
             cmd = [CLANGXX, *COMMON, *HOST_DEFS, "-c", str(s), "-o", str(o)]
-        if _stale(o, [s, *hdrs], cmd):
+        if _stale(o, [s, *hdrs, *(CSRC / i for i in INCLUDED.get(src, []))], cmd):
             jobs.append((o, cmd))
 
     def job(item):

@@ -526,6 +526,77 @@ int yrt_render(yrt_scene* s, const yrt_render_params* p, float* out, int mem, vo
     });
 }
 
+static_assert(YRT_AOV_COUNT == yrt::aov_count && YRT_AOV_DEPTH == yrt::aov_depth &&
+                  YRT_AOV_POSITION == yrt::aov_position && YRT_AOV_NORMAL == yrt::aov_normal &&
+                  YRT_AOV_TEXCOORD == yrt::aov_texcoord && YRT_AOV_ALBEDO == yrt::aov_albedo &&
+                  YRT_AOV_IDS == yrt::aov_ids,
+              "the kernel's plane order is the header's");
+
+int yrt_render_aovs(yrt_scene* s, const yrt_render_params* p, unsigned mask, const yrt_aov_planes* out, int mem,
+                    void* stream) {
+    if (!s || !p || !out) return YRT_ERR_INVALID_ARG;
+    return guarded([&] {
+        if (mask == 0 || mask >> YRT_AOV_COUNT) throw std::invalid_argument("aov mask must name one to all of YRT_AOV_*");
+        for (int k = 0; k < YRT_AOV_COUNT; k++)
+            if ((mask >> k & 1) && !out->plane[k]) throw std::invalid_argument("a requested aov's plane is null");
+        auto r = resolve(*s->ds, *p);
+        hipStream_t st = (hipStream_t)stream;
+        hip_check(hipSetDevice(s->ds->device), "hipSetDevice");
+        yrt::dev_render_args a = {};
+        a.cam = yrt::make_dev_camera(s->ds->cameras[p->camera]);
+        a.width = r.W;
+        a.height = r.H;
+        a.samples = p->samples;
+        a.x0 = r.x0;
+        a.tile_w = r.tw;
+        a.y0 = r.y0;
+        a.tile_h = r.th;
+        a.band = p->band;
+        a.band_stride = p->band_stride;
+        a.band_offset = p->band_offset;
+        a.out_stride = p->out_stride > 0 ? p->out_stride : r.tw;
+        if (a.out_stride < r.tw) throw std::invalid_argument("out_stride smaller than the window width");
+        // the counters are zeroed whatever the window: an empty one (a band offset without
+        // bands) launches nothing, and yrt_last_stats must not then report the call before
+        hip_check(hipMemsetAsync(s->counters, 0, yrt::cnt_slots * yrt::cnt_count * sizeof(unsigned long long), st),
+                  "hipMemsetAsync");
+        s->last_stream = st;
+        if (r.tw <= 0 || r.th <= 0) return YRT_OK;
+        yrt::dev_aov_planes dp = {};
+        if (mem == YRT_MEM_DEVICE) {
+            for (int k = 0; k < YRT_AOV_COUNT; k++) dp.plane[k] = (mask >> k & 1) ? out->plane[k] : nullptr;
+            hip_check(yrt::launch_aovs(*s->ds, a, mask, dp, s->counters, st), "aov kernel launch");
+            return YRT_OK;
+        }
+        // host planes: device staging of their own (the handle's scratch stays yrt_render's),
+        // copied back and released
+        const size_t bytes = (size_t)a.out_stride * r.th * 16;
+        struct staging {
+            void* p = nullptr;
+            ~staging() {
+                if (p) (void)hipFree(p);
+            }
+        } stage;
+        hip_check(hipMalloc(&stage.p, bytes * __builtin_popcount(mask)), "hipMalloc(aov staging)");
+        size_t used = 0;
+        for (int k = 0; k < YRT_AOV_COUNT; k++)
+            if (mask >> k & 1) dp.plane[k] = (char*)stage.p + bytes * used++;
+        // padding columns (out_stride > tile_w) keep the caller's bytes: they are staged too
+        if (a.out_stride > r.tw)
+            for (int k = 0; k < YRT_AOV_COUNT; k++)
+                if (mask >> k & 1)
+                    hip_check(hipMemcpyAsync(dp.plane[k], out->plane[k], bytes, hipMemcpyHostToDevice, st), "hipMemcpyAsync");
+        hipError_t e = yrt::launch_aovs(*s->ds, a, mask, dp, s->counters, st);
+        for (int k = 0; k < YRT_AOV_COUNT && e == hipSuccess; k++)
+            if (mask >> k & 1) e = hipMemcpyAsync(out->plane[k], dp.plane[k], bytes, hipMemcpyDeviceToHost, st);
+        // the staging is released only after the stream has drained, also on an error
+        const hipError_t e2 = hipStreamSynchronize(st);
+        hip_check(e, "aov render");
+        hip_check(e2, "hipStreamSynchronize");
+        return YRT_OK;
+    });
+}
+
 static int trace_impl(yrt_scene* s, const float* rays, int n, int any, unsigned char* hit, int* inst, int* ei,
                       float* ew, float* dist, int mem, void* stream) {
     if (!s || n < 0 || (n && (!rays || !hit))) return YRT_ERR_INVALID_ARG;

@@ -5,12 +5,14 @@
 // same options, defaults (720, 1, 0.1, out.png), messages and output file as the
 // reference, over the C++ mirror in include/yrt_raytrace.hpp. Extra options (not in
 // the reference): --device N, --width W, --max-depth D, --algorithm
-// wavefront|megakernel|wavefront_lane, --time (print GPU time and Mrays/s).
+// wavefront|megakernel|wavefront_lane, --time (print GPU time and Mrays/s), --aov LIST
+// (the camera hit's geometry buffers as .npy files beside the image).
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <string>
+#include <vector>
 
 #include "yrt_raytrace.hpp"
 
@@ -29,7 +31,9 @@ namespace {
             "  --width N            explicit width (default round(aspect * resolution))\n"
             "  --max-depth N        cap on reflection depth [16]\n"
             "  --algorithm NAME     wavefront | megakernel | wavefront_lane [wavefront]\n"
-            "  --time               print render time and Mrays/s\n");
+            "  --time               print render time and Mrays/s\n"
+            "  --aov LIST           also write OUT.<name>.npy, (H, W, 4) float32 (ids: int32), for each of\n"
+            "                       depth,position,normal,texcoord,albedo,ids (one GPU)\n");
     exit(msg ? 1 : 0);
 }
 
@@ -40,12 +44,48 @@ int parse_int(const char* s, const char* opt) {
     return (int)v;
 }
 
+const char* const aov_names[YRT_AOV_COUNT] = {"depth", "position", "normal", "texcoord", "albedo", "ids"};
+
+// --aov's comma-separated names as the YRT_AOV_* bit mask
+unsigned parse_aovs(const std::string& list) {
+    unsigned mask = 0;
+    for (size_t at = 0; at <= list.size();) {
+        size_t end = list.find(',', at);
+        if (end == std::string::npos) end = list.size();
+        const std::string name = list.substr(at, end - at);
+        int k = 0;
+        while (k < YRT_AOV_COUNT && name != aov_names[k]) k++;
+        if (k == YRT_AOV_COUNT) usage(("unknown --aov " + name).c_str());
+        mask |= 1u << k;
+        at = end + 1;
+    }
+    return mask;
+}
+
+// a (h, w, 4) array of 4-byte elements as a NumPy format 1.0 file, C order: the magic, the
+// version, the header dict's length, the dict padded with spaces so that the data starts on
+// a multiple of 64 bytes, a newline, the data
+void save_npy(const std::string& path, const void* data, int w, int h, const char* descr) {
+    std::string dict = std::string("{'descr': '") + descr + "', 'fortran_order': False, 'shape': (" +
+                       std::to_string(h) + ", " + std::to_string(w) + ", 4), }";
+    while ((10 + dict.size() + 1) % 64) dict += ' ';
+    dict += '\n';
+    const unsigned char head[10] = {0x93, 'N', 'U', 'M', 'P', 'Y', 1, 0, (unsigned char)(dict.size() & 0xff),
+                                    (unsigned char)(dict.size() >> 8)};
+    FILE* f = fopen(path.c_str(), "wb");
+    const size_t bytes = (size_t)w * h * 16;
+    const bool ok = f && fwrite(head, 1, sizeof head, f) == sizeof head &&
+                    fwrite(dict.data(), 1, dict.size(), f) == dict.size() && fwrite(data, 1, bytes, f) == bytes;
+    if ((f && fclose(f) != 0) || !ok) throw yrt_cpp::error(YRT_ERR_IO, "cannot write " + path);
+}
+
 }  // namespace
 
 int main(int argc, char** argv) {
     int resolution = 720, samples = 1, device = 0, gpus = 1, width = 0, max_depth = 16, algorithm = YRT_ALGO_WAVEFRONT;
     float amb = 0.1f;
     bool timing = false;
+    unsigned aovs = 0;
     std::string out = "out.png", scenein;
     for (int k = 1; k < argc; k++) {
         std::string a = argv[k];
@@ -68,6 +108,7 @@ int main(int argc, char** argv) {
             else if (n == "wavefront_lane") algorithm = YRT_ALGO_WAVEFRONT_LANE;
             else usage("unknown --algorithm");
         } else if (a == "--time") timing = true;
+        else if (a == "--aov") aovs = parse_aovs(val());
         else if (a == "-h" || a == "--help") usage(nullptr);
         else if (!a.empty() && a[0] == '-') usage(("unknown option " + a).c_str());
         else if (scenein.empty()) scenein = a;
@@ -75,6 +116,7 @@ int main(int argc, char** argv) {
     }
     if (scenein.empty()) scenein = "scene.obj";  // the reference's default positional value
     if (gpus < 1) usage("--gpus must be >= 1");
+    if (aovs && gpus > 1) usage("--aov renders on one GPU (--gpus 1)");
     try {
         printf("loading scene %s\n", scenein.c_str());
         auto scn = yrt_cpp::load_scene(scenein);
@@ -100,6 +142,28 @@ int main(int argc, char** argv) {
         }
         printf("saving image %s\n", out.c_str());
         yrt_cpp::save_hdr_or_ldr(out, hdr);
+        if (aovs) {
+            // the requested planes in host memory, each saved as <output without extension>.<name>.npy
+            yrt_render_params p = scn->params;
+            p.resolution = resolution;
+            p.samples = samples;
+            const size_t slash = out.find_last_of('/'), dot = out.find_last_of('.');
+            const std::string stem = dot != std::string::npos && (slash == std::string::npos || dot > slash)
+                                         ? out.substr(0, dot)
+                                         : out;
+            std::vector<std::vector<char>> planes(YRT_AOV_COUNT);
+            yrt_aov_planes ap = {};
+            for (int k = 0; k < YRT_AOV_COUNT; k++)
+                if (aovs >> k & 1) {
+                    planes[k].resize((size_t)hdr.width * hdr.height * 16);
+                    ap.plane[k] = planes[k].data();
+                }
+            yrt_cpp::check(yrt_render_aovs(scn->on_device(), &p, aovs, &ap, YRT_MEM_HOST, nullptr), "render_aovs");
+            for (int k = 0; k < YRT_AOV_COUNT; k++)
+                if (aovs >> k & 1)
+                    save_npy(stem + "." + aov_names[k] + ".npy", planes[k].data(), hdr.width, hdr.height,
+                             k == YRT_AOV_IDS ? "<i4" : "<f4");
+        }
     } catch (const yrt_cpp::error& e) {
         fprintf(stderr, "%s\n", e.what());
         return 1;

@@ -341,3 +341,6 @@ hipError_t launch_tonemap(const float* rgba, int n, unsigned char* out, const to
 }
 
 }  // namespace yrt
+
+// the AOV pass (k_aov, launch_aovs): a file of its own in this translation unit
+#include "aov.hip"

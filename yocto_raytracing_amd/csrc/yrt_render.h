@@ -110,6 +110,25 @@ hipError_t launch_tonemap(const float* rgba, int n, unsigned char* out, const to
 // the .hdr writer's RGBE bytes on the device (rgbe.h; the layout of rgbe_encode)
 hipError_t launch_rgbe(const float* rgba, int w, int h, unsigned char* out, hipStream_t stream);
 
+// the AOV pass (aov.hip k_aov): the planes of yrt_render_aovs in the order of YRT_AOV_*,
+// 16 bytes per pixel each (float4, ids int4), window layout and out_stride of launch_render;
+// only the planes whose bit is set in `mask` are read or written. The caller zeroes the
+// counter lines before the launch; an empty window launches nothing.
+enum aov_index {
+    aov_depth = 0,
+    aov_position = 1,
+    aov_normal = 2,
+    aov_texcoord = 3,
+    aov_albedo = 4,
+    aov_ids = 5,
+    aov_count = 6
+};
+struct dev_aov_planes {
+    void* plane[aov_count];
+};
+hipError_t launch_aovs(const device_scene& ds, const dev_render_args& args, unsigned mask, const dev_aov_planes& out,
+                       unsigned long long* counters, hipStream_t stream);
+
 // mirror levels the megakernel records per lane (render.hip); the wavefront pipeline
 // keeps per-level records in HBM and takes any max_depth
 constexpr int megakernel_max_depth = 16;
