@@ -1,0 +1,252 @@
+"""The kept kernel variants and the multi-chunk render loop, run on small frames.
+
+tools/build_variants.py builds four libraries beside the default one (TEST_VARIANTS): the
+compiled descent loops instead of descent_asm.h / wide_asm.h, the closest hit's stack with
+lane masks, the any-hit grid's items as (block, light) pairs, and `chunks`, whose run()
+splits a frame into chunks of 2^11 samples (YRT_CHUNK_LOG2 / YRT_MIRROR_CHUNK_LOG2). Every
+library, the default one included, runs the same cases in a fresh child process
+(tests/variant_worker.py, YRT_LIB naming the library), one child at a time. The frames are
+37 x 24 pixels: 5 x 3 tiles of 8 x 8, partial on both axes; at 2^11 samples per chunk 4 spp
+are chunks of 8 and 7 tiles (shade fused), 9 spp chunks of 4, 4, 4 and 3 tiles that straddle
+tile rows (k_accumulate runs).
+
+Asserted per library: the frame, the counts and the trace records equal the default
+library's bit for bit; the frame and the counts equal the oracle's (helpers.ATOL / RTOL;
+the bit-exact fraction of these 3.5 K channels is printed, not asserted); the primary phase
+was launched once per chunk of run()'s cap_for formula -- more than once for `chunks`, once
+for every other library; the tile lists were on and off as asked.
+
+A child that ends by a signal, an abort, a time limit or any error fails its test with the
+child's stderr, and every later test of this module then fails without starting a child.
+"""
+from __future__ import annotations
+
+import importlib.util
+import json
+import os
+import re
+import subprocess
+import sys
+from functools import lru_cache
+
+import numpy as np
+import pytest
+
+from helpers import GOLDEN, MIRROR_DEPTH, ROOT, Oracle, assert_same_floats, close_mask
+
+RES, WIDTH = 24, 37
+TILE = 8
+CHILD_TIMEOUT = 300  # seconds: the child loads torch, uploads five scenes and renders ~50 tiny frames
+
+
+def _tool():
+    spec = importlib.util.spec_from_file_location("yrt_build_variants", ROOT / "tools" / "build_variants.py")
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    return mod
+
+
+TOOL = _tool()
+LIBS = ("default", *TOOL.TEST_VARIANTS)
+
+
+def _render(cid, scene, samples, max_depth=16, lists="auto", algorithm="wavefront", count_work=False):
+    return {"id": cid, "kind": "render", "scene": scene, "resolution": RES, "width": WIDTH, "samples": samples,
+            "max_depth": max_depth, "lists": lists, "algorithm": algorithm, "count_work": count_work}
+
+
+def _cases():
+    out = []
+    for scene in ("simple", "instance1k"):
+        for s in (2, 3):
+            for lists in ("on", "off"):
+                out.append(_render(f"{scene}-s{s}-{lists}", scene, s, lists=lists))
+    out.append(_render("lines-s3", "lines", 3))
+    for lists in ("on", "off"):
+        out.append(_render(f"refl-s2-{lists}", "refl", 2, lists=lists))
+    out.append(_render("mirrors-s2", "mirrors", 2, max_depth=MIRROR_DEPTH))
+    out.append(_render("simple-s2-lane", "simple", 2, algorithm="wavefront_lane"))
+    out.append(_render("simple-s2-count", "simple", 2, count_work=True))
+    for rays, scene in (("ref_rays_instance10000", "instance10000"), ("ref_rays_lines", "lines"),
+                        ("ref_rays_degenerate_instance10000", "instance10000")):
+        out.append({"id": rays, "kind": "trace", "scene": scene, "rays": f"{rays}.npz"})
+    return out
+
+
+CASES = {c["id"]: c for c in _cases()}
+RENDER_IDS = [k for k, c in CASES.items() if c["kind"] == "render"]
+TRACE_IDS = [k for k, c in CASES.items() if c["kind"] == "trace"]
+REFLECTIVE = ("refl", "mirrors")  # the scenes with kr > 0: run() chunks them by YRT_MIRROR_CHUNK_LOG2
+
+
+# ---- build and load: no GPU needed ----
+
+@lru_cache(maxsize=None)
+def variant_libs():
+    paths = TOOL.main(TOOL.test_specs(), default_library=False, verbose=False)
+    return dict(zip(TOOL.TEST_VARIANTS, paths))
+
+
+def lib_path(lib):
+    return ROOT / "yocto_raytracing_amd" / "libyrt.so" if lib == "default" else variant_libs()[lib]
+
+
+@pytest.mark.skipif(not os.path.exists(TOOL.b.HIPCC), reason="hipcc not installed")
+def test_variants_build_and_link():
+    """every variant compiles and links for gfx950, loads, and exports the C-ABI's render entry;
+    a second build finds nothing to do"""
+    import ctypes
+
+    libs = variant_libs()
+    assert list(libs) == list(TOOL.TEST_VARIANTS)
+    for name, path in libs.items():
+        assert path.exists() and path.parent.name == "variants", path
+        so = ctypes.CDLL(str(path))
+        assert so.yrt_render and so.yrt_last_stats and so.yrt_trace_first, name
+    stamps = {p: p.stat().st_mtime_ns for p in libs.values()}
+    TOOL.main(TOOL.test_specs(), default_library=False, verbose=False)
+    assert stamps == {p: p.stat().st_mtime_ns for p in libs.values()}, "an unchanged variant was rebuilt"
+    assert TOOL.MAX_WORKERS <= 16
+
+
+# ---- one child per library ----
+
+_results = {}
+_dead = None  # why no further child is started
+
+
+def results(lib, tmp_path_factory):
+    global _dead
+    if lib in _results:
+        return _results[lib]
+    if _dead:
+        pytest.fail(f"no child is started after a failed one: {_dead}")
+    path = lib_path(lib)
+    assert path.exists(), f"{path}: build the library first"
+    d = tmp_path_factory.mktemp(f"variant_{lib}")
+    cases, out = d / "cases.json", d / "out.npz"
+    cases.write_text(json.dumps(list(CASES.values())))
+    env = dict(os.environ, YRT_LIB=str(path))
+    cmd = [sys.executable, str(ROOT / "tests" / "variant_worker.py"), str(cases), str(out)]
+    try:
+        r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=CHILD_TIMEOUT)
+    except subprocess.TimeoutExpired as e:
+        _dead = f"the {lib} child ran into its {CHILD_TIMEOUT} s limit"
+        err = e.stderr.decode(errors="replace") if isinstance(e.stderr, bytes) else (e.stderr or "")
+        pytest.fail(f"{_dead}\n{err[-4000:]}")
+    if r.returncode != 0:
+        _dead = f"the {lib} child ended with status {r.returncode}"
+        pytest.fail(f"{_dead}\n{r.stderr[-4000:]}")
+    z = np.load(out)
+    res = {"meta": json.loads(str(z["meta"])), "z": z}
+    assert res["meta"]["library"] == str(path)
+    _results[lib] = res
+    return res
+
+
+@lru_cache(maxsize=None)
+def oracle_render(scene, samples, max_depth):
+    return Oracle(scene).render(RES, samples, width=WIDTH, max_depth=max_depth)
+
+
+def _define(lib, knob):
+    """the knob's value in `lib`: its define, or the default in wavefront.hip"""
+    for d in TOOL.TEST_VARIANTS.get(lib, []):
+        m = re.fullmatch(rf"-D{knob}=(\d+)", d)
+        if m:
+            return int(m.group(1))
+    src = (ROOT / "yocto_raytracing_amd" / "csrc" / "wavefront.hip").read_text()
+    return int(re.search(rf"#define {knob} (\d+)", src).group(1))
+
+
+def expected_chunks(lib, case):
+    """run()'s cap_for: whole tiles of at most target / spp pixels per chunk"""
+    spp = case["samples"] ** 2
+    npix_total = -(-WIDTH // TILE) * -(-RES // TILE) * TILE * TILE
+    knob = "YRT_MIRROR_CHUNK_LOG2" if case["scene"] in REFLECTIVE else "YRT_CHUNK_LOG2"
+    pix = max(1, min(npix_total, (1 << _define(lib, knob)) // spp))
+    pix = -(-pix // (TILE * TILE)) * TILE * TILE
+    return -(-npix_total // pix)
+
+
+def test_chunk_formula_splits_these_frames():
+    """the `chunks` library's frames are 2 chunks at 4 spp and 4 at 9 spp, reflective or not;
+    every other library renders them as one"""
+    for cid in RENDER_IDS:
+        c = CASES[cid]
+        assert expected_chunks("chunks", c) == {2: 2, 3: 4}[c["samples"]], cid
+        for lib in LIBS:
+            if lib != "chunks":
+                assert expected_chunks(lib, c) == 1, (lib, cid)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("lib,cid", [(lib, cid) for lib in LIBS for cid in RENDER_IDS])
+def test_render_case(lib, cid, tmp_path_factory):
+    c = CASES[cid]
+    base = results("default", tmp_path_factory)
+    got = results(lib, tmp_path_factory)
+    img, m = got["z"][f"{cid}.img"], got["meta"]["cases"][cid]
+    st = m["stats"]
+    # the oracle (for the default library too)
+    ref, nrays, trunc = oracle_render(c["scene"], c["samples"], c["max_depth"])
+    assert img.shape == ref.shape == (RES, WIDTH, 4)
+    exact = float(np.mean(img.view(np.uint32) == ref.view(np.uint32)))
+    print(f"{lib} {cid}: bit-exact fraction vs oracle {exact:.5f}, primary launches {m['launches'].get('primary')}")
+    assert st["rays"] == nrays
+    assert st["depth_truncated"] == trunc
+    assert st["camera_samples"] == RES * WIDTH * c["samples"] ** 2
+    assert close_mask(img, ref).all(), f"max|diff| {np.abs(img.astype(np.float64) - ref).max()}"
+    # the default library, bit for bit
+    bm = base["meta"]["cases"][cid]
+    np.testing.assert_array_equal(img.view(np.uint32), base["z"][f"{cid}.img"].view(np.uint32))
+    keys = ["rays", "camera_samples", "shadow_rays", "depth_truncated", "stack_overflow"]
+    if c["count_work"]:
+        keys += ["box_tests", "instance_entries", "prim_tests"]
+        assert st["box_tests"] > 0 and st["prim_tests"] > 0
+    assert {k: st[k] for k in keys} == {k: bm["stats"][k] for k in keys}
+    # one primary launch per chunk
+    n = expected_chunks(lib, c)
+    assert (n > 1) == (lib == "chunks")
+    assert m["launches"]["primary"] == n, m["launches"]
+    if c["samples"] ** 2 == 9 or c["scene"] in REFLECTIVE:  # unfused shade: k_accumulate per chunk
+        assert m["launches"]["accumulate"] == n, m["launches"]
+    else:
+        assert "accumulate" not in m["launches"], m["launches"]
+    # the lists as asked
+    tl, btl = m["tile_lists"], bm["tile_lists"]
+    if c["lists"] == "off":
+        assert not tl["camera"] and not tl["bundles"], tl
+    else:
+        assert (tl["camera"], tl["bundles"]) == (btl["camera"], btl["bundles"]), (tl, btl)
+    if c["scene"] == "instance1k" and c["lists"] == "on":  # (its lists are built: test_gpu_lists.py)
+        assert tl["camera"] and tl["bundles"], tl
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("lib,cid", [(lib, cid) for lib in LIBS for cid in TRACE_IDS])
+def test_trace_case(lib, cid, tmp_path_factory):
+    """the reference's records exactly, as tests/test_gpu_parity.py states it, and the default
+    library's"""
+    base = results("default", tmp_path_factory)["z"]
+    got = results(lib, tmp_path_factory)["z"]
+    z = np.load(GOLDEN / CASES[cid]["rays"])
+    first = {k: got[f"{cid}.first.{k}"] for k in ("hit", "inst", "ei", "ew", "dist")}
+    h = z["hit"] > 0
+    np.testing.assert_array_equal(first["hit"], z["hit"].astype(bool))
+    np.testing.assert_array_equal(first["ei"][h], z["ei"][h])
+    np.testing.assert_array_equal(first["inst"][h], z["inst"][h])
+    if "degenerate" in cid:
+        assert_same_floats(first["ew"][h], z["ew"][h])
+        assert_same_floats(first["dist"][h], z["dist"][h])
+    else:
+        np.testing.assert_array_equal(first["inst"], np.where(h, z["inst"], -1))
+        np.testing.assert_array_equal(first["ei"], z["ei"])
+        np.testing.assert_array_equal(first["ew"][h].view(np.uint32), z["ew"][h].view(np.uint32))
+        np.testing.assert_array_equal(first["dist"][h].view(np.uint32), z["dist"][h].view(np.uint32))
+    np.testing.assert_array_equal(got[f"{cid}.any"], z["any_hit"].astype(bool))
+    for k in ("hit", "inst", "ei"):
+        np.testing.assert_array_equal(first[k], base[f"{cid}.first.{k}"])
+    for k in ("ew", "dist"):
+        assert_same_floats(first[k], base[f"{cid}.first.{k}"])
+    np.testing.assert_array_equal(got[f"{cid}.any"], base[f"{cid}.any"])

@@ -64,7 +64,18 @@ constexpr int shadow_block() { return PACKET ? YRT_SHADOW_BLOCK : WF_BLOCK; }
 // 8 / 16 / 32 / 64 / 128 / 256 / 512: -2.8 / -2.7 / -2.6 / -2.7 / -2.2 / -1.0 / 0 %)
 #define YRT_SHADOW_BLOCK_CHUNK 16
 #endif
-constexpr int CHUNK_LOG2 = 29;  // samples per chunk, non-reflective scenes (~70 B of HBM each)
+// samples per chunk (host side only: run() splits a frame by them). Small values are for the
+// tests, which run frames of a few tiles as several chunks (tests/test_gpu_variants.py)
+#ifndef YRT_CHUNK_LOG2
+#define YRT_CHUNK_LOG2 29  // non-reflective scenes (~70 B of HBM per sample)
+#endif
+#ifndef YRT_MIRROR_CHUNK_LOG2
+#define YRT_MIRROR_CHUNK_LOG2 25  // reflective scenes (64 B more per sample and mirror level)
+#endif
+constexpr int CHUNK_LOG2 = YRT_CHUNK_LOG2;
+constexpr int MIRROR_CHUNK_LOG2 = YRT_MIRROR_CHUNK_LOG2;
+static_assert(CHUNK_LOG2 >= 0 && CHUNK_LOG2 <= 29 && MIRROR_CHUNK_LOG2 >= 0 && MIRROR_CHUNK_LOG2 <= 29,
+              "a chunk's samples are counted in an int");
 constexpr int TILE = 8;         // pixel tiles of TILE x TILE in the sample enumeration
 
 // the render's list sums (k_list_stats, yrt_scene_tile_lists / yrt_scene_tile_list_masks):
@@ -2243,9 +2254,10 @@ hipError_t run(device_scene& ds, const dev_render_args& A, float4* out, unsigned
     // samples per chunk: a whole frame at c3/c4, 15 chunks at c5. A reflective scene keeps
     // per-level records for every level (64 B per sample and level). The chunk is halved
     // until the workspace takes at most half of the free HBM (deep mirror recursions run
-    // as more, smaller chunks); a depth whose smallest chunk (2^16 samples) still does not
-    // fit is refused.
-    long long target = ds.reflective ? (1ll << 25) : (1ll << CHUNK_LOG2);
+    // as more, smaller chunks); a depth whose smallest chunk (2^16 samples, or the knob's
+    // own target when that starts lower: the halving never raises it) still does not fit is
+    // refused.
+    long long target = 1ll << (ds.reflective ? MIRROR_CHUNK_LOG2 : CHUNK_LOG2);
     auto cap_for = [&](long long tgt) {
         int pix = (int)std::max<long long>(1, std::min<long long>(npix_total, tgt / spp));
         pix = ((pix + TILE * TILE - 1) / (TILE * TILE)) * TILE * TILE;
@@ -2510,7 +2522,11 @@ hipError_t run(device_scene& ds, const dev_render_args& A, float4* out, unsigned
 
 hipError_t launch_render_wavefront(device_scene& ds, const dev_render_args& args, void* out_rgba,
                                    unsigned long long* counters, bool count_work, bool packet, hipStream_t stream) {
-    if (args.tile_w <= 0 || args.tile_h <= 0) return hipSuccess;
+    // an empty window (a band offset without bands): no chunk, so no k_chunk_setup -- the
+    // counters still start at 0, or yrt_last_stats would report the render before this one
+    if (args.tile_w <= 0 || args.tile_h <= 0)
+        return counters ? hipMemsetAsync(counters, 0, (size_t)cnt_slots * cnt_count * sizeof(unsigned long long), stream)
+                        : hipSuccess;
     float4* out = (float4*)out_rgba;
     if (packet) {
         // the per-wave stack holds 32-bit node indices: no narrow/wide split needed
