@@ -294,6 +294,34 @@ typedef struct yrt_aov_planes { void* plane[YRT_AOV_COUNT]; } yrt_aov_planes; /*
 int yrt_render_aovs(yrt_scene* ds, const yrt_render_params* p, unsigned mask, const yrt_aov_planes* out, int mem,
                     void* stream);
 
+/* ---- shading passes: the beauty split into the terms shade() adds up ----
+ * One render gives the beauty and, per pixel, the box filter (the float32 sum over the s*s
+ * camera samples, jj outer and ii inner, from +0, divided by float(s*s)) of each term of the
+ * level-0 shade() call (raytrace.cpp:88-211), in the reference's operations and order:
+ *   DIRECT      c after the light loop: from +0, c = c + (ld + ls) per unoccluded light
+ *   DIFFUSE     the same chain over the same lights with ld alone
+ *   SPECULAR    the same chain with ls alone
+ *   REFLECTION  the vector added at raytrace.cpp:203, col * kr, col the whole recursive shade()
+ *               of the mirror ray; 0 * kr where max_depth cuts the ray; +0 without kr
+ *   AMBIENT     la = amb * kd (* its kd_txt lookup)
+ * A sample that misses adds +0 to every pass. With s = 1, beauty == (DIRECT + REFLECTION) +
+ * AMBIENT in float32, bit for bit. .w is 1 for a pixel of the image; local rows past the image
+ * edge read as zeros, as in yrt_render. */
+enum { YRT_PASS_DIRECT = 0, YRT_PASS_DIFFUSE = 1, YRT_PASS_SPECULAR = 2,
+       YRT_PASS_REFLECTION = 3, YRT_PASS_AMBIENT = 4, YRT_PASS_COUNT = 5 };
+typedef struct yrt_pass_planes { float* plane[YRT_PASS_COUNT]; } yrt_pass_planes; /* RGBA f32, 16 B per pixel */
+/* mask: bit 1 << YRT_PASS_x per requested pass, one to all five; only their planes are read
+ * from `out` and written (anything else: YRT_ERR_INVALID_ARG). `beauty`, when not NULL, receives
+ * exactly what yrt_render writes for the same `p`, from the same walk. Every field of `p` means
+ * what it means in yrt_render, except that the algorithm is YRT_ALGO_WAVEFRONT or
+ * YRT_ALGO_WAVEFRONT_LANE and count_work is 0 (otherwise YRT_ERR_UNSUPPORTED). Planes have the
+ * layout of yrt_render's output (row-major window, out_stride; padding columns keep the
+ * caller's bytes). Host planes make the call synchronous, device planes are stream-ordered. An
+ * empty window leaves the planes untouched. yrt_last_stats and yrt_last_timings then report
+ * what they report after yrt_render of the same `p`. */
+int yrt_render_passes(yrt_scene* ds, const yrt_render_params* p, unsigned mask, const yrt_pass_planes* out,
+                      float* beauty /* may be NULL */, int mem, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

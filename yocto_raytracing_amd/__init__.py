@@ -23,7 +23,7 @@ from . import _native as N
 from ._native import RenderParams, Stats, YrtError, check
 
 __all__ = [
-    "Scene", "DeviceScene", "load_scene", "build_bvh", "raytrace", "render_aovs", "intersect_first",
+    "Scene", "DeviceScene", "load_scene", "build_bvh", "raytrace", "render_aovs", "render_passes", "intersect_first",
     "intersect_any", "tonemap", "save_hdr_or_ldr", "render_params", "device_count", "YrtError",
 ]
 
@@ -236,6 +236,18 @@ class DeviceScene:
         check(N.lib.yrt_render_aovs(self._h, C.byref(params), mask, C.byref(ap), mem, C.c_void_p(stream or 0)),
               "yrt_render_aovs")
 
+    def render_passes_into(self, params: RenderParams, planes: dict, beauty_ptr: Optional[int] = None,
+                           device_memory: bool = True, stream: Optional[int] = None) -> None:
+        """Launch raytrace() with its shading passes (yrt_render_passes) into caller planes
+        {name: pointer}, RGBA float32 each in render_into's layout; only the named passes are
+        written. `beauty_ptr`, when given, receives render_into's image from the same walk."""
+        mask, pp = _pass_mask(planes), N.PassPlanes()
+        for name, ptr in planes.items():
+            pp.plane[N.PASSES[name]] = ptr
+        mem = N.YRT_MEM_DEVICE if device_memory else N.YRT_MEM_HOST
+        check(N.lib.yrt_render_passes(self._h, C.byref(params), mask, C.byref(pp), C.c_void_p(beauty_ptr or 0), mem,
+                                      C.c_void_p(stream or 0)), "yrt_render_passes")
+
     def last_timings(self) -> dict:
         """per-phase GPU ms of the last render with timing=True: {phase: (ms, launches)}"""
         t = N.Timings()
@@ -412,6 +424,47 @@ def render_aovs(scn, resolution: int = 720, samples: int = 1, *, aovs: Sequence[
         w, h = window[2] or W - window[0], window[3] or H - window[1]
     out = {n: np.zeros((h, w, 4), np.int32 if n == "ids" else np.float32) for n in aovs}
     ds.render_aovs_into(p, {n: a.ctypes.data for n, a in out.items()}, device_memory=False)
+    return out
+
+
+def _pass_mask(names) -> int:
+    """the YRT_PASS_* bit mask of pass names; an unknown name raises before any native call"""
+    names = list(names)
+    bad = [n for n in names if n not in N.PASSES]
+    if bad or not names:
+        raise ValueError((f"unknown pass {bad[0]!r}" if bad else "no pass named") + f" (one of {', '.join(N.PASSES)})")
+    mask = 0
+    for n in names:
+        mask |= 1 << N.PASSES[n]
+    return mask
+
+
+def render_passes(scn, amb: Sequence[float] = (0.1, 0.1, 0.1), resolution: int = 720, samples: int = 1, *,
+                  passes: Sequence[str] = tuple(N.PASSES), beauty: bool = True, width: int = 0, max_depth: int = 16,
+                  camera: int = 0, window=None, algorithm: str = "wavefront", devices=None, device: int = 0) -> dict:
+    """raytrace with its lighting split: {name: (H, W, 4) float32} for "direct" (diffuse +
+    specular per light), "diffuse", "specular", "reflection" (the mirror ray's colour times
+    kr) and "ambient", each the box filter of that term of shade() (raytrace.cpp:88-211), and
+    with `beauty` the image raytrace gives, under "beauty", from the same render. At one sample
+    per pixel beauty == (direct + reflection) + ambient in float32. One GPU: `devices` is not
+    supported (shard with a window or bands instead)."""
+    _pass_mask(passes)
+    if devices is not None:
+        raise ValueError("render_passes renders on one GPU: devices= is not supported")
+    ds = _device_scene(scn, device)
+    p = render_params(amb, resolution, samples, width=width, max_depth=max_depth, camera=camera, window=window,
+                      algorithm=algorithm)
+    W, H = ds.image_size(p)
+    if window is None:
+        w, h = W, H
+    else:
+        w, h = window[2] or W - window[0], window[3] or H - window[1]
+    out = {n: np.zeros((h, w, 4), np.float32) for n in passes}
+    img = np.zeros((h, w, 4), np.float32) if beauty else None
+    ds.render_passes_into(p, {n: a.ctypes.data for n, a in out.items()},
+                          beauty_ptr=img.ctypes.data if beauty else None, device_memory=False)
+    if beauty:
+        out["beauty"] = img
     return out
 
 

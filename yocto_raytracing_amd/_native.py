@@ -97,8 +97,17 @@ class AovPlanes(C.Structure):
     _fields_ = [("plane", C.c_void_p * YRT_AOV_COUNT)]
 
 
+# YRT_PASS_*: name -> plane index (bit of the mask); every plane is RGBA float32
+PASSES = {"direct": 0, "diffuse": 1, "specular": 2, "reflection": 3, "ambient": 4}
+YRT_PASS_COUNT = 5
+
+
+class PassPlanes(C.Structure):
+    _fields_ = [("plane", C.c_void_p * YRT_PASS_COUNT)]
+
+
 _vp = C.c_void_p
-_ip = C.POINTER(C.c_int)
+_ip =C.POINTER(C.c_int)
 _sig = {
     "yrt_abi_version": (C.c_int, []),
     "yrt_status_string": (C.c_char_p, [C.c_int]),
@@ -145,6 +154,7 @@ _sig = {
     "yrt_multi_last_timings": (C.c_int, [_vp, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
     "yrt_render_multi": (C.c_int, [_vp, _ip, C.c_int, C.POINTER(RenderParams), _vp, C.c_int]),
     "yrt_render_aovs": (C.c_int, [_vp, C.POINTER(RenderParams), C.c_uint, C.POINTER(AovPlanes), C.c_int, _vp]),
+    "yrt_render_passes": (C.c_int, [_vp, C.POINTER(RenderParams), C.c_uint, C.POINTER(PassPlanes), _vp, C.c_int, _vp]),
 }
 EXPORTS = tuple(_sig)
 

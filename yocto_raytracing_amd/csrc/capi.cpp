@@ -597,6 +597,97 @@ int yrt_render_aovs(yrt_scene* s, const yrt_render_params* p, unsigned mask, con
     });
 }
 
+static_assert(YRT_PASS_COUNT == yrt::pass_count && YRT_PASS_DIRECT == yrt::pass_direct &&
+                  YRT_PASS_DIFFUSE == yrt::pass_diffuse && YRT_PASS_SPECULAR == yrt::pass_specular &&
+                  YRT_PASS_REFLECTION == yrt::pass_reflection && YRT_PASS_AMBIENT == yrt::pass_ambient,
+              "the kernel's plane order is the header's");
+
+int yrt_render_passes(yrt_scene* s, const yrt_render_params* p, unsigned mask, const yrt_pass_planes* out, float* beauty,
+                      int mem, void* stream) {
+    if (!s || !p || !out) return YRT_ERR_INVALID_ARG;
+    if (mask == 0 || mask >> YRT_PASS_COUNT) {
+        g_last_error = "pass mask must name one to all of YRT_PASS_*";
+        return YRT_ERR_INVALID_ARG;
+    }
+    for (int k = 0; k < YRT_PASS_COUNT; k++)
+        if ((mask >> k & 1) && !out->plane[k]) {
+            g_last_error = "a requested pass's plane is null";
+            return YRT_ERR_INVALID_ARG;
+        }
+    return guarded([&] {
+        if (p->algorithm == YRT_ALGO_MEGAKERNEL)
+            throw yrt::unsupported_error("the shading passes run in the wavefront algorithms");
+        if (p->algorithm != YRT_ALGO_WAVEFRONT && p->algorithm != YRT_ALGO_WAVEFRONT_LANE)
+            throw std::invalid_argument("unknown algorithm");
+        if (p->count_work != 0) throw yrt::unsupported_error("the shading passes do not count work");
+        auto r = resolve(*s->ds, *p);
+        hipStream_t st = (hipStream_t)stream;
+        hip_check(hipSetDevice(s->ds->device), "hipSetDevice");
+        yrt::dev_render_args a = {};
+        a.cam = yrt::make_dev_camera(s->ds->cameras[p->camera]);
+        for (int k = 0; k < 3; k++) a.amb[k] = p->ambient[k];
+        a.width = r.W;
+        a.height = r.H;
+        a.samples = p->samples;
+        a.max_depth = p->max_depth > 0 ? p->max_depth : 16;
+        a.x0 = r.x0;
+        a.tile_w = r.tw;
+        a.y0 = r.y0;
+        a.tile_h = r.th;
+        a.band = p->band;
+        a.band_stride = p->band_stride;
+        a.band_offset = p->band_offset;
+        a.out_stride = p->out_stride > 0 ? p->out_stride : r.tw;
+        if (a.out_stride < r.tw) throw std::invalid_argument("out_stride smaller than the window width");
+        if (!(p->timing == 2 && s->ds->timer.on)) s->ds->timer.reset(p->timing != 0);
+        const bool packet = p->algorithm == YRT_ALGO_WAVEFRONT;
+        s->last_stream = st;
+        yrt::dev_pass_planes dp = {};
+        if (mem == YRT_MEM_DEVICE || r.tw <= 0 || r.th <= 0) {
+            // (an empty window launches nothing but the counters' memset: the planes are not touched)
+            for (int k = 0; k < YRT_PASS_COUNT; k++) dp.plane[k] = (mask >> k & 1) ? out->plane[k] : nullptr;
+            hip_check(yrt::launch_render_wavefront_passes(*s->ds, a, mask, dp, beauty, s->counters, packet, st),
+                      "passes render launch");
+            return YRT_OK;
+        }
+        // host planes: device staging of their own (the handle's scratch stays yrt_render's),
+        // copied back and released
+        const size_t bytes = (size_t)a.out_stride * r.th * 16;
+        struct staging {
+            void* p = nullptr;
+            ~staging() {
+                if (p) (void)hipFree(p);
+            }
+        } stage;
+        hip_check(hipMalloc(&stage.p, bytes * (__builtin_popcount(mask) + (beauty ? 1 : 0))), "hipMalloc(pass staging)");
+        size_t used = 0;
+        float* host[YRT_PASS_COUNT + 1] = {};
+        float* dev[YRT_PASS_COUNT + 1] = {};
+        for (int k = 0; k <= YRT_PASS_COUNT; k++) {
+            host[k] = k < YRT_PASS_COUNT ? ((mask >> k & 1) ? out->plane[k] : nullptr) : beauty;
+            if (host[k]) dev[k] = (float*)((char*)stage.p + bytes * used++);
+            if (k < YRT_PASS_COUNT) dp.plane[k] = dev[k];
+        }
+        // padding columns (out_stride > tile_w) keep the caller's bytes: they are staged too
+        if (a.out_stride > r.tw)
+            for (int k = 0; k <= YRT_PASS_COUNT; k++)
+                if (host[k]) hip_check(hipMemcpyAsync(dev[k], host[k], bytes, hipMemcpyHostToDevice, st), "hipMemcpyAsync");
+        hipError_t e = hipSuccess;
+        try {
+            e = yrt::launch_render_wavefront_passes(*s->ds, a, mask, dp, dev[YRT_PASS_COUNT], s->counters, packet, st);
+        } catch (...) {
+            (void)hipStreamSynchronize(st);  // the staging is released only after the stream has drained
+            throw;
+        }
+        for (int k = 0; k <= YRT_PASS_COUNT && e == hipSuccess; k++)
+            if (host[k]) e = hipMemcpyAsync(host[k], dev[k], bytes, hipMemcpyDeviceToHost, st);
+        const hipError_t e2 = hipStreamSynchronize(st);
+        hip_check(e, "passes render");
+        hip_check(e2, "hipStreamSynchronize");
+        return YRT_OK;
+    });
+}
+
 static int trace_impl(yrt_scene* s, const float* rays, int n, int any, unsigned char* hit, int* inst, int* ei,
                       float* ew, float* dist, int mem, void* stream) {
     if (!s || n < 0 || (n && (!rays || !hit))) return YRT_ERR_INVALID_ARG;

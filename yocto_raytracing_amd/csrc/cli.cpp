@@ -6,7 +6,8 @@
 // reference, over the C++ mirror in include/yrt_raytrace.hpp. Extra options (not in
 // the reference): --device N, --width W, --max-depth D, --algorithm
 // wavefront|megakernel|wavefront_lane, --time (print GPU time and Mrays/s), --aov LIST
-// (the camera hit's geometry buffers as .npy files beside the image).
+// (the camera hit's geometry buffers as .npy files beside the image), --passes LIST (the
+// image's lighting split, from the same render, as .npy files beside it).
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -33,7 +34,10 @@ namespace {
             "  --algorithm NAME     wavefront | megakernel | wavefront_lane [wavefront]\n"
             "  --time               print render time and Mrays/s\n"
             "  --aov LIST           also write OUT.<name>.npy, (H, W, 4) float32 (ids: int32), for each of\n"
-            "                       depth,position,normal,texcoord,albedo,ids (one GPU)\n");
+            "                       depth,position,normal,texcoord,albedo,ids (one GPU)\n"
+            "  --passes LIST        also write OUT.<name>.npy, (H, W, 4) float32, for each of\n"
+            "                       direct,diffuse,specular,reflection,ambient, from the image's own render\n"
+            "                       (one GPU, a wavefront algorithm)\n");
     exit(msg ? 1 : 0);
 }
 
@@ -56,6 +60,24 @@ unsigned parse_aovs(const std::string& list) {
         int k = 0;
         while (k < YRT_AOV_COUNT && name != aov_names[k]) k++;
         if (k == YRT_AOV_COUNT) usage(("unknown --aov " + name).c_str());
+        mask |= 1u << k;
+        at = end + 1;
+    }
+    return mask;
+}
+
+const char* const pass_names[YRT_PASS_COUNT] = {"direct", "diffuse", "specular", "reflection", "ambient"};
+
+// --passes' comma-separated names as the YRT_PASS_* bit mask
+unsigned parse_passes(const std::string& list) {
+    unsigned mask = 0;
+    for (size_t at = 0; at <= list.size();) {
+        size_t end = list.find(',', at);
+        if (end == std::string::npos) end = list.size();
+        const std::string name = list.substr(at, end - at);
+        int k = 0;
+        while (k < YRT_PASS_COUNT && name != pass_names[k]) k++;
+        if (k == YRT_PASS_COUNT) usage(("unknown --passes " + name).c_str());
         mask |= 1u << k;
         at = end + 1;
     }
@@ -85,7 +107,7 @@ int main(int argc, char** argv) {
     int resolution = 720, samples = 1, device = 0, gpus = 1, width = 0, max_depth = 16, algorithm = YRT_ALGO_WAVEFRONT;
     float amb = 0.1f;
     bool timing = false;
-    unsigned aovs = 0;
+    unsigned aovs = 0, passes = 0;
     std::string out = "out.png", scenein;
     for (int k = 1; k < argc; k++) {
         std::string a = argv[k];
@@ -109,6 +131,7 @@ int main(int argc, char** argv) {
             else usage("unknown --algorithm");
         } else if (a == "--time") timing = true;
         else if (a == "--aov") aovs = parse_aovs(val());
+        else if (a == "--passes") passes = parse_passes(val());
         else if (a == "-h" || a == "--help") usage(nullptr);
         else if (!a.empty() && a[0] == '-') usage(("unknown option " + a).c_str());
         else if (scenein.empty()) scenein = a;
@@ -117,6 +140,8 @@ int main(int argc, char** argv) {
     if (scenein.empty()) scenein = "scene.obj";  // the reference's default positional value
     if (gpus < 1) usage("--gpus must be >= 1");
     if (aovs && gpus > 1) usage("--aov renders on one GPU (--gpus 1)");
+    if (passes && gpus > 1) usage("--passes renders on one GPU (--gpus 1)");
+    if (passes && algorithm == YRT_ALGO_MEGAKERNEL) usage("--passes needs a wavefront algorithm, not --algorithm megakernel");
     try {
         printf("loading scene %s\n", scenein.c_str());
         auto scn = yrt_cpp::load_scene(scenein);
@@ -129,8 +154,31 @@ int main(int argc, char** argv) {
         scn->params.algorithm = algorithm;
         printf("tracing scene\n");
         if (timing) yrt_cpp::raytrace(scn, {amb, amb, amb}, resolution, samples);  // upload + warm up
+        const size_t slash = out.find_last_of('/'), dot = out.find_last_of('.');
+        const std::string stem =
+            dot != std::string::npos && (slash == std::string::npos || dot > slash) ? out.substr(0, dot) : out;
+        std::vector<std::vector<float>> pass_data(YRT_PASS_COUNT);
         auto t0 = std::chrono::steady_clock::now();
-        auto hdr = yrt_cpp::raytrace(scn, {amb, amb, amb}, resolution, samples);
+        yrt_cpp::image4f hdr;
+        if (passes) {
+            // one render: the image and its passes in host memory
+            yrt_render_params p = scn->params;
+            p.ambient[0] = p.ambient[1] = p.ambient[2] = amb;
+            p.resolution = resolution;
+            p.samples = samples;
+            int w = 0, h = 0;
+            yrt_cpp::check(yrt_image_size(scn->on_device(), &p, &w, &h), "raytrace");
+            hdr = yrt_cpp::image4f(w, h);
+            yrt_pass_planes pp = {};
+            for (int k = 0; k < YRT_PASS_COUNT; k++)
+                if (passes >> k & 1) {
+                    pass_data[k].resize((size_t)w * h * 4);
+                    pp.plane[k] = pass_data[k].data();
+                }
+            yrt_cpp::check(yrt_render_passes(scn->on_device(), &p, passes, &pp, &hdr.pixels[0].x, YRT_MEM_HOST, nullptr),
+                           "render_passes");
+        } else
+            hdr = yrt_cpp::raytrace(scn, {amb, amb, amb}, resolution, samples);
         auto t1 = std::chrono::steady_clock::now();
         if (timing) {
             const yrt_stats st = yrt_cpp::last_stats(scn);
@@ -142,15 +190,14 @@ int main(int argc, char** argv) {
         }
         printf("saving image %s\n", out.c_str());
         yrt_cpp::save_hdr_or_ldr(out, hdr);
+        for (int k = 0; k < YRT_PASS_COUNT; k++)
+            if (passes >> k & 1)
+                save_npy(stem + "." + pass_names[k] + ".npy", pass_data[k].data(), hdr.width, hdr.height, "<f4");
         if (aovs) {
             // the requested planes in host memory, each saved as <output without extension>.<name>.npy
             yrt_render_params p = scn->params;
             p.resolution = resolution;
             p.samples = samples;
-            const size_t slash = out.find_last_of('/'), dot = out.find_last_of('.');
-            const std::string stem = dot != std::string::npos && (slash == std::string::npos || dot > slash)
-                                         ? out.substr(0, dot)
-                                         : out;
             std::vector<std::vector<char>> planes(YRT_AOV_COUNT);
             yrt_aov_planes ap = {};
             for (int k = 0; k < YRT_AOV_COUNT; k++)

@@ -2164,6 +2164,286 @@ __global__ __launch_bounds__(WF_BLOCK) void k_accumulate(dev_render_args A, chun
         valid ? make_float4(acc.x / d, acc.y / d, acc.z / d, 1.0f) : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
 }
 
+// ---- shading passes (yrt_render_passes): the beauty split into the terms shade() adds up ----
+// Per camera sample: DIRECT is c after the light loop (raytrace.cpp:121-185), DIFFUSE and
+// SPECULAR the same chain of adds over the same lights with ld or ls alone, REFLECTION the
+// vector added at raytrace.cpp:203 (col * kr; 0 * kr where max_depth cuts the mirror ray, +0
+// on a material that does not reflect), AMBIENT la. A miss adds +0 to every pass. Each plane
+// is the beauty's box filter of its value: the ordered sum over jj/ii divided by float(s*s).
+// The beauty is plane pass_count of the same kernels, computed exactly as k_shade and
+// k_accumulate compute it. The kernels below are k_shade's and k_accumulate's bodies again,
+// not a shared function: the beauty path keeps the code it has.
+constexpr int pass_planes = pass_count + 1;  // the five passes and the beauty
+struct pass_buffers {
+    unsigned mask;            // bit k: plane k is wanted (bit pass_count: the beauty)
+    float4* out[pass_planes];  // the caller's planes (window layout, out_stride); null when not wanted
+    f4* smp[pass_count];      // per-sample values of a wanted pass (unfused and mirror shapes only)
+};
+
+// fused k_shade_passes: 70-72 VGPRs and no scratch; at k_shade's 7 waves the two more
+// accumulators (d, s) put 32 bytes per lane into scratch
+constexpr int shade_pass_waves = 6;
+template <bool FUSE, int SB = WF_BLOCK, bool OCC4 = false>
+__global__ __launch_bounds__(SB, FUSE ? shade_pass_waves : YRT_SHADE_LEVEL_WAVES) void k_shade_passes(
+    dev_scene_view S, dev_render_args A, int level, int nsamp_level0, int max_depth, wf_buffers B, pass_buffers P,
+    unsigned long long* counters, chunk_args C) {
+    // the per-sample values of a block's whole pixels, one row of SB floats per (plane,
+    // component): 12 bytes per sample and plane, 18 KiB for the six planes, so eight blocks
+    // still fit a CU's 160 KiB and the LDS does not bound the kernel's 6 waves per SIMD. The
+    // rows are one float apart in the banks, so the 18 chains of a pixel read 18 banks
+    constexpr int ROW = SB + 1;
+    __shared__ float fused[FUSE ? pass_planes * 3 * ROW : 1];
+    __shared__ int cmp_count[SB / 64], cmp_base[SB / 64];
+    __shared__ float srgb_lds[YRT_SHADE_LDS_SRGB ? 256 : 1];
+    const float* lut = YRT_SHADE_LDS_SRGB ? srgb_lds : S.srgb;
+    if (YRT_SHADE_LDS_SRGB && S.ntextures > 0) {  // uniform over the grid
+        for (int q = (int)threadIdx.x; q < 256; q += SB) srgb_lds[q] = S.srgb[q];
+        __syncthreads();
+    }
+    work_counts wc;
+    unsigned long long truncated = 0;
+    const vec3f amb = {A.amb[0], A.amb[1], A.amb[2]};
+    const vec3f cam_o = {A.cam.ox, A.cam.oy, A.cam.oz};
+    const int stride = gridDim.x * SB;
+    const int gout = (int)(blockIdx.x % (unsigned)level_segments);
+    const int nseg = FUSE ? 1 : level ? level_segments : 1;
+    for (int g = 0; g < nseg; g++) {
+    const int n = (!FUSE && level) ? *seg_counter(B.count, level, g) : nsamp_level0;
+    const int nround = (n + stride - 1) / stride;
+    for (int round = 0; round < nround; round++) {
+        const int j = round * stride + blockIdx.x * SB + threadIdx.x;
+        const int idx = FUSE ? j : g * B.seg + j;
+        bool spawn = false;
+        vec3f p = {0, 0, 0}, dr = {0, 0, 0}, rec_d = {0, 0, 0}, rec_la = {0, 0, 0};
+        int rec_mat = 0;
+        // this sample's pass values (level 0): a miss and a lane past the chunk keep +0
+        vec3f R = {0, 0, 0}, pc = {0, 0, 0}, pd = {0, 0, 0}, ps = {0, 0, 0}, pr = {0, 0, 0}, pla = {0, 0, 0};
+        if (j < n) {
+            float4 s0 = ld4s(B.surf0 + idx);
+            uint32_t occ_bits = 0;
+            if constexpr (OCC4) {
+#pragma unroll
+                for (int q = 0; q < 4; q++) {
+                    const int lq = q < S.nlights ? q : 0;  // an unconditional load, masked after
+                    const uint32_t ob = ldb(B.occl + (size_t)lq * B.capacity + idx);
+                    occ_bits |= (q < S.nlights && ob != 0u) ? 1u << q : 0u;
+                }
+            }
+            const int info = sample_state(s0);
+            bool write_r = info != -2;
+            const float4 ro4 = (!FUSE && level) ? ld4(B.ray_o(level) + idx) : make_float4(cam_o.x, cam_o.y, cam_o.z, 0.0f);
+            if (info >= 0) {
+                vec3f nrm;
+                vec2f uv;
+                int mat, kind;
+                if (YRT_HIT16) {
+                    const surface sf = hit16_surface(S, s0);
+                    p = sf.p, nrm = sf.n, uv = sf.uv, mat = sf.mat, kind = sf.kind;
+                } else {
+                    const float4 s1 = ld4s(B.surf1 + idx);
+                    p = xyz(s0), nrm = xyz(s1), uv = {s1.w, (!YRT_SKIP_UNUSED_V || B.need_v) ? lds1(B.surfv + idx) : 0.0f};
+                    mat = info_mat(info), kind = info & 3;
+                }
+                const vec3f ro = xyz(ro4);
+                const float4 m0 = ld4(S.mats + 4 * mat), m1 = ld4(S.mats + 4 * mat + 1);
+                const float4 m2 = ld4(S.mats + 4 * mat + 2), m3 = ld4(S.mats + 4 * mat + 3);
+                const vec3f kd0 = xyz(m0), ks0 = xyz(m1), kr = xyz(m2);
+                const float ns = m0.w;
+                const int kd_txt = ibits(m1.w), ks_txt = ibits(m2.w);
+                const bool reflective = ibits(m3.w) & mat_reflective;
+                vec3f la = amb * kd0;
+                vec3f tkd = {1, 1, 1}, tks = {1, 1, 1};
+                if (kd_txt >= 0) {
+                    tkd = eval_texture<false>(S, kd_txt, uv, wc, lut);
+                    la = la * tkd;
+                }
+                if (ks_txt >= 0) tks = eval_texture<false>(S, ks_txt, uv, wc, lut);
+                vec3f c = {0.0f, 0.0f, 0.0f}, cd = {0.0f, 0.0f, 0.0f}, cs = {0.0f, 0.0f, 0.0f};
+                vec3f v;
+                float vlen;
+                normalize_len(ro - p, v, vlen);
+                for (int li = 0; li < S.nlights; li++) {
+                    if (OCC4 ? ((occ_bits >> li) & 1u) != 0u : ldb(B.occl + (size_t)li * B.capacity + idx) != 0) continue;
+                    const f4* lr = S.lights + 6 * li;
+                    float4 lrec[6];
+                    ld_scalar<6>(lr, lrec);
+                    frame3f lf = {xyz(lrec[0]), xyz(lrec[1]), xyz(lrec[2]), xyz(lrec[3])};
+                    vec3f lp0 = xyz(lrec[4]), ke = xyz(lrec[5]);
+                    vec3f tp = transform_point(lf, lp0 - p);
+                    vec3f l, h;
+                    float r, hlen;
+                    normalize_len(tp, l, r);
+                    normalize_len(v + l, h, hlen);
+                    vec3f kd = kd0, ks = ks0;
+                    if (kd_txt >= 0) kd = kd * tkd;
+                    if (ks_txt >= 0) ks = ks * tks;
+                    const vec3f ker = div3(ke, r * r);
+                    vec3f ld = kd * ker;
+                    vec3f ls = ks * ker;
+                    if (kind == kind_lines) {
+                        float prodnl = dot(nrm, l);
+                        float prodnh = dot(nrm, h);
+                        if (prodnl < 0.0f) prodnl *= -1;
+                        if (prodnh < 0.0f) prodnh *= -1;
+                        float sinnl = __builtin_sqrtf(1.0f - prodnl);
+                        float sinnh = __builtin_sqrtf(1.0f - prodnh);
+                        ld = ld * sinnl;
+                        ls = ls * spec_pow(sinnh, ns, ls);
+                    } else {
+                        ld = ld * smax(0.0f, dot(nrm, l));
+                        ls = ls * spec_pow(smax(0.0f, dot(nrm, h)), ns, ls);
+                    }
+                    c = c + (ld + ls);
+                    cd = cd + ld;
+                    cs = cs + ls;
+                }
+                pc = c, pd = cd, ps = cs, pla = la;
+                if (!reflective) {
+                    R = c + la;
+                } else if (FUSE || level + 1 >= max_depth || level + 1 >= B.nlevels) {
+                    // depth cap: the reflected contribution counts as a miss (col = 0)
+                    truncated++;
+                    vec3f t = {0.0f * kr.x, 0.0f * kr.y, 0.0f * kr.z};
+                    pr = t;
+                    R = (c + t) + la;
+                } else {
+                    spawn = true;
+                    dr = (nrm * 2.0f * dot(nrm, v)) - v;
+                    rec_d = c;
+                    rec_la = la;
+                    rec_mat = mat;
+                    write_r = false;
+                }
+            }
+            if (!FUSE && level == 0 && info != -2) {
+                // level 0's values per sample; a sample that spawns a mirror ray gets its
+                // reflection value where the fold reaches it
+                if (P.mask >> pass_direct & 1) gstore(P.smp[pass_direct], idx, pc.x, pc.y, pc.z, 0.0f);
+                if (P.mask >> pass_diffuse & 1) gstore(P.smp[pass_diffuse], idx, pd.x, pd.y, pd.z, 0.0f);
+                if (P.mask >> pass_specular & 1) gstore(P.smp[pass_specular], idx, ps.x, ps.y, ps.z, 0.0f);
+                if (P.mask >> pass_ambient & 1) gstore(P.smp[pass_ambient], idx, pla.x, pla.y, pla.z, 0.0f);
+                if ((P.mask >> pass_reflection & 1) && !spawn) gstore(P.smp[pass_reflection], idx, pr.x, pr.y, pr.z, 0.0f);
+            }
+            if (!FUSE && write_r) {
+                // the fold of k_shade (R_k-1 = (D + R_k * kr) + la); its last step, into the
+                // camera sample, adds that sample's reflection value
+                vec3f col = R;
+                int lev = level, node = idx;
+                while (lev > 0) {
+                    const int parent = ibits(B.ray_o(lev)[node].w);
+                    const float4 d = ld4(B.rec0(lev - 1) + parent);
+                    const float4 la = ld4(B.rec1(lev - 1) + parent);
+                    const float4 kr = ld4(S.mats + 4 * ibits(d.w) + 2);  // the parent's material kr
+                    vec3f cc = {d.x, d.y, d.z};
+                    const vec3f t = {col.x * kr.x, col.y * kr.y, col.z * kr.z};
+                    if (lev == 1 && (P.mask >> pass_reflection & 1))
+                        gstore(P.smp[pass_reflection], parent, t.x, t.y, t.z, 0.0f);
+                    cc = cc + t;
+                    cc = cc + xyz(la);
+                    col = cc, node = parent, lev--;
+                }
+                B.rad[node] = {col.x, col.y, col.z, 1.0f};
+            }
+        }
+        if constexpr (FUSE) {
+            // (one round per block: the rows are written once)
+            auto put = [&](int k, const vec3f& val) {
+                if (!(P.mask >> k & 1)) return;  // (uniform)
+                fused[(k * 3 + 0) * ROW + threadIdx.x] = val.x;
+                fused[(k * 3 + 1) * ROW + threadIdx.x] = val.y;
+                fused[(k * 3 + 2) * ROW + threadIdx.x] = val.z;
+            };
+            put(pass_direct, pc), put(pass_diffuse, pd), put(pass_specular, ps);
+            put(pass_reflection, pr), put(pass_ambient, pla), put(pass_count, R);
+            continue;  // one level: no mirror rays
+        }
+        const unsigned long long mask = __ballot(spawn);
+        const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
+        if (spawn) {
+            B.rec0(level)[idx] = {rec_d.x, rec_d.y, rec_d.z, __int_as_float(rec_mat)};
+            B.rec1(level)[idx] = {rec_la.x, rec_la.y, rec_la.z, 0};
+        }
+        if (lane == 0) cmp_count[w] = __popcll(mask);
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            int tot = 0;
+            for (int q = 0; q < SB / 64; q++) tot += cmp_count[q];
+            int acc = tot ? atomicAdd(seg_counter(B.count, level + 1, gout), tot) : 0;
+            for (int q = 0; q < SB / 64; q++) cmp_base[q] = acc, acc += cmp_count[q];
+        }
+        __syncthreads();
+        if (spawn) {
+            const int slot = gout * B.seg + cmp_base[w] + __popcll(mask & ((1ull << lane) - 1));
+            B.ray_o(level + 1)[slot] = {p.x, p.y, p.z, __int_as_float(idx)};
+            B.ray_d(level + 1)[slot] = {dr.x, dr.y, dr.z, 0};
+        }
+    }
+    }
+    if (FUSE) {
+        // raytrace.cpp:232-249 per plane: one lane per (pixel, plane, colour component), each
+        // lane's sum the reference's ordered chain of adds for that component
+        __syncthreads();
+        const int ppb = SB / C.spp;
+        for (int t = (int)threadIdx.x; t < 3 * pass_planes * ppb; t += SB) {
+            const int px = t / (3 * pass_planes), r = t - 3 * pass_planes * px;
+            const int k = r / 3, comp = r - 3 * k;
+            if (!(P.mask >> k & 1)) continue;
+            const int pl = (int)(blockIdx.x * SB / C.spp) + px;
+            int lx, ly, i, j;
+            const bool valid = pl < C.npix && pixel_of(A, C.tiles_x, C.pix0 + pl, lx, ly, i, j);
+            if (pl < C.npix && lx < A.tile_w && ly < A.tile_h) {
+                float v = 0.0f;
+                if (valid) {
+                    const float* row = fused + (k * 3 + comp) * ROW + px * C.spp;
+                    float acc = 0.0f;
+                    for (int q = 0; q < C.spp; q++) acc = acc + row[q];
+                    v = acc / float(C.spp);
+                }
+                float* o = reinterpret_cast<float*>(P.out[k] + (size_t)ly * A.out_stride + lx);
+                o[comp] = v;
+                if (comp == 0) o[3] = valid ? 1.0f : 0.0f;
+            }
+        }
+    }
+    flush(counters, cnt_depth_truncated, truncated);
+}
+
+// k_accumulate per plane: blockIdx.y is the plane, its samples P.smp[k] (the beauty's B.rad)
+__global__ __launch_bounds__(WF_BLOCK) void k_accumulate_passes(dev_render_args A, chunk_args C, wf_buffers B,
+                                                                pass_buffers P) {
+    __shared__ float4 stage[WF_BLOCK / 64][64 * (AQ + 1)];  // rows padded against bank conflicts
+    const int k = (int)blockIdx.y;
+    if (!(P.mask >> k & 1)) return;  // (uniform over the block)
+    const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int pl0 = blockIdx.x * WF_BLOCK + w * 64;
+    const int np = max(0, min(64, C.npix - pl0));  // pixels of this wave
+    float4* S = stage[w];
+    const f4* base = (k == pass_count ? B.rad : P.smp[k]) + (size_t)pl0 * C.spp;
+    vec3f acc = {0, 0, 0};
+    for (int q0 = 0; q0 < C.spp; q0 += AQ) {  // the same trip count in every wave of the block
+        const int qn = min(AQ, C.spp - q0);
+        for (int e = lane; e < np * qn; e += 64) {
+            const int px = e / qn, q = e % qn;
+            S[px * (AQ + 1) + q] = ld4(base + (size_t)px * C.spp + q0 + q);
+        }
+        __syncthreads();
+        if (lane < np)
+            for (int q = 0; q < qn; q++) {
+                const float4 c = S[lane * (AQ + 1) + q];
+                acc = {acc.x + c.x, acc.y + c.y, acc.z + c.z};
+            }
+        __syncthreads();
+    }
+    if (lane >= np) return;
+    const int pl = pl0 + lane;
+    int lx, ly, i, j;
+    const bool valid = pixel_of(A, C.tiles_x, C.pix0 + pl, lx, ly, i, j);
+    if (lx >= A.tile_w || ly >= A.tile_h) return;
+    const float d = float(C.spp);
+    P.out[k][(size_t)ly * A.out_stride + lx] =
+        valid ? make_float4(acc.x / d, acc.y / d, acc.z / d, 1.0f) : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+}
+
 size_t align_up(size_t x) { return (x + 255) & ~size_t(255); }
 
 // the per-level, per-segment mirror-ray counters (seg_counter)
@@ -2178,7 +2458,11 @@ size_t super_count(int cap) { return (bundle_count(cap) + super_bundles - 1) / s
 // camera lists: 8x8-pixel tiles of a chunk of cap samples at spp samples per pixel
 size_t camera_tiles(int cap, int spp) { return ((size_t)cap / (size_t)spp + TILE * TILE - 1) / (TILE * TILE); }
 
-size_t workspace_bytes(int cap, int spp, int nlights, int nlevels) {
+// pass_planes_n planes of pass_samples per-sample pass values (yrt_render_passes in the unfused
+// and mirror shapes) follow yrt_render's workspace, which is the same with or without them
+size_t workspace_bytes(int cap, int spp, int nlights, int nlevels, int pass_planes_n = 0, size_t pass_samples = 0) {
+    if (pass_planes_n > 0)
+        return workspace_bytes(cap, spp, nlights, nlevels) + (size_t)pass_planes_n * align_up(16 * pass_samples);
     size_t c = (size_t)cap;
     size_t b = align_up(count_bytes(nlevels)) + align_up(32 * sizeof(unsigned)) +
                align_up(list_sums * sizeof(unsigned long long));
@@ -2241,9 +2525,11 @@ wf_buffers carve(void* base, int cap, int spp, int nlights, int nlevels) {
     return B;
 }
 
+// passes: yrt_render_passes' planes (P.mask, P.out; out is then P.out[pass_count], the beauty,
+// or null), shaded by k_shade_passes and summed by k_accumulate_passes; null: yrt_render
 template <bool COUNT, bool PACKET, typename SE>
 hipError_t run(device_scene& ds, const dev_render_args& A, float4* out, unsigned long long* counters,
-               hipStream_t stream) {
+               hipStream_t stream, const pass_buffers* passes = nullptr) {
     const int spp = A.samples * A.samples;
     const int tiles_x = (A.tile_w + TILE - 1) / TILE;
     const int tiles_y = (A.tile_h + TILE - 1) / TILE;
@@ -2270,7 +2556,16 @@ hipError_t run(device_scene& ds, const dev_render_args& A, float4* out, unsigned
     // segments) at most cap / 8 + 8 * 256
     auto seg_of = [&](int pix) { return pix * spp / level_segments + level_segments * WF_BLOCK; };
     auto cap_of = [&](int pix) { return nlevels > 1 ? level_segments * seg_of(pix) : pix * spp; };
-    auto bytes_of = [&](long long tgt) { return workspace_bytes(cap_of(cap_for(tgt)), spp, ds.nlights, nlevels); };
+    // one level and whole pixels per block: shade sums the pixels itself (k_shade FUSE;
+    // one-wave fused blocks lose: +9 %)
+    const bool fuse = nlevels == 1 && WF_BLOCK % spp == 0;
+    // the passes' per-sample planes (16 B per wanted pass and sample; the fused shape keeps
+    // them in LDS)
+    const int smp_planes = passes && !fuse ? __builtin_popcount(passes->mask & ((1u << pass_count) - 1)) : 0;
+    auto bytes_of = [&](long long tgt) {
+        const int pix = cap_for(tgt);
+        return workspace_bytes(cap_of(pix), spp, ds.nlights, nlevels, smp_planes, (size_t)pix * spp);
+    };
     // the free-memory query (a driver round trip) only when the workspace must grow: a
     // steady frame loop reuses the workspace it already has
     if (bytes_of(target) > ds.work_bytes) {
@@ -2286,7 +2581,7 @@ hipError_t run(device_scene& ds, const dev_render_args& A, float4* out, unsigned
     const int pix_per_chunk = cap_for(target);
     const int seg = seg_of(pix_per_chunk);
     const int cap = cap_of(pix_per_chunk);
-    const size_t need = workspace_bytes(cap, spp, ds.nlights, nlevels);
+    const size_t need = workspace_bytes(cap, spp, ds.nlights, nlevels, smp_planes, (size_t)pix_per_chunk * spp);
     if (need > ds.work_bytes) {
         if (ds.work) (void)hipFree(ds.work);
         ds.work = nullptr;
@@ -2299,6 +2594,13 @@ hipError_t run(device_scene& ds, const dev_render_args& A, float4* out, unsigned
     B.trel = ds.trel;
     B.seg = seg;
     B.need_v = ds.view.ntextures > 0;
+    pass_buffers P = {};
+    if (passes) {
+        P = *passes;
+        char* at = (char*)ds.work + workspace_bytes(cap, spp, ds.nlights, nlevels);
+        for (int k = 0; k < pass_count && smp_planes; k++)
+            if (P.mask >> k & 1) P.smp[k] = (f4*)at, at += align_up(16 * (size_t)pix_per_chunk * spp);
+    }
     bool list_stats = false;
     ds.last_camera_lists = ds.last_bundles = false;
     if (!ds.list_stats_host) {
@@ -2328,9 +2630,6 @@ hipError_t run(device_scene& ds, const dev_render_args& A, float4* out, unsigned
     ds.last_lds_staging = 0;
     const float4 cam4 = make_float4(A.cam.ox, A.cam.oy, A.cam.oz, 0.0f);
     const int stride_grid = 2048;  // grid-stride kernels: 8 blocks of 256 per CU
-    // one level and whole pixels per block: shade sums the pixels itself (k_shade FUSE;
-    // one-wave fused blocks lose: +9 %)
-    const bool fuse = nlevels == 1 && WF_BLOCK % spp == 0;
     if (npix_total == 0 && counters) {  // (no chunk, so no k_chunk_setup: the counters still start at 0)
         hipError_t e = hipMemsetAsync(counters, 0, (size_t)cnt_slots * cnt_count * sizeof(unsigned long long), stream);
         if (e != hipSuccess) return e;
@@ -2479,11 +2778,28 @@ hipError_t run(device_scene& ds, const dev_render_args& A, float4* out, unsigned
             hipLaunchKernelGGL((k_shade<COUNT, FU, SBV, false>), GRID, dim3(SBV), 0, stream, ds.view, A, level,      \
                                nsamp, A.max_depth, B, counters, C, out);                                        \
     } while (0)
-            if (fuse) {
+#define YRT_SHADE_PASSES_LAUNCH(FU, GRID)                                                                          \
+    do {                                                                                                          \
+        if (occ4)                                                                                                 \
+            hipLaunchKernelGGL((k_shade_passes<FU, WF_BLOCK, true>), GRID, dim3(WF_BLOCK), 0, stream, ds.view, A, level, \
+                               nsamp, A.max_depth, B, P, counters, C);                                            \
+        else                                                                                                      \
+            hipLaunchKernelGGL((k_shade_passes<FU, WF_BLOCK, false>), GRID, dim3(WF_BLOCK), 0, stream, ds.view, A,  \
+                               level, nsamp, A.max_depth, B, P, counters, C);                                     \
+    } while (0)
+            if (passes) {
+                if constexpr (!COUNT) {  // (launch_render_wavefront_passes never counts work)
+                    if (fuse)
+                        YRT_SHADE_PASSES_LAUNCH(true, dim3(grid));
+                    else
+                        YRT_SHADE_PASSES_LAUNCH(false, dim3(level ? stride_grid : grid));
+                }
+            } else if (fuse) {
                 YRT_SHADE_LAUNCH(true, WF_BLOCK, dim3(grid));
             } else {
                 YRT_SHADE_LAUNCH(false, WF_BLOCK, dim3(level ? stride_grid : grid));
             }
+#undef YRT_SHADE_PASSES_LAUNCH
 #undef YRT_SHADE_LAUNCH
             T.end(t, stream);
             if (level + 1 < nlevels) {
@@ -2497,8 +2813,12 @@ hipError_t run(device_scene& ds, const dev_render_args& A, float4* out, unsigned
         }
         if (!fuse) {
             t = T.begin(phase_accumulate, stream);
-            hipLaunchKernelGGL(k_accumulate, dim3((C.npix + WF_BLOCK - 1) / WF_BLOCK), dim3(WF_BLOCK), 0, stream, A,
-                               C, B, out);
+            if (passes)
+                hipLaunchKernelGGL(k_accumulate_passes, dim3((C.npix + WF_BLOCK - 1) / WF_BLOCK, pass_planes),
+                                   dim3(WF_BLOCK), 0, stream, A, C, B, P);
+            else
+                hipLaunchKernelGGL(k_accumulate, dim3((C.npix + WF_BLOCK - 1) / WF_BLOCK), dim3(WF_BLOCK), 0, stream, A,
+                                   C, B, out);
             T.end(t, stream);
         }
         if (B.cam_lists || B.bundles) {
@@ -2538,6 +2858,22 @@ hipError_t launch_render_wavefront(device_scene& ds, const dev_render_args& args
                           : run<false, false, uint16_t>(ds, args, out, counters, stream);
     return count_work ? run<true, false, uint32_t>(ds, args, out, counters, stream)
                       : run<false, false, uint32_t>(ds, args, out, counters, stream);
+}
+
+hipError_t launch_render_wavefront_passes(device_scene& ds, const dev_render_args& args, unsigned mask,
+                                          const dev_pass_planes& out, void* beauty_rgba, unsigned long long* counters,
+                                          bool packet, hipStream_t stream) {
+    if (args.tile_w <= 0 || args.tile_h <= 0)  // (an empty window: as launch_render_wavefront)
+        return counters ? hipMemsetAsync(counters, 0, (size_t)cnt_slots * cnt_count * sizeof(unsigned long long), stream)
+                        : hipSuccess;
+    pass_buffers P = {};
+    P.mask = (mask & ((1u << pass_count) - 1)) | (beauty_rgba ? 1u << pass_count : 0u);
+    for (int k = 0; k < pass_count; k++) P.out[k] = (mask >> k & 1) ? (float4*)out.plane[k] : nullptr;
+    P.out[pass_count] = (float4*)beauty_rgba;
+    float4* beauty = (float4*)beauty_rgba;
+    if (packet) return run<false, true, uint32_t>(ds, args, beauty, counters, stream, &P);
+    if (ds.narrow_stack) return run<false, false, uint16_t>(ds, args, beauty, counters, stream, &P);
+    return run<false, false, uint32_t>(ds, args, beauty, counters, stream, &P);
 }
 
 }  // namespace yrt

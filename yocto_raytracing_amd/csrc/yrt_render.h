@@ -140,4 +140,23 @@ constexpr int traversal_stack_cap = 40;
 hipError_t launch_render_wavefront(device_scene& ds, const dev_render_args& args, void* out_rgba,
                                    unsigned long long* counters, bool count_work, bool packet, hipStream_t stream);
 
+// the shading passes (wavefront.hip k_shade_passes / k_accumulate_passes): the planes of
+// yrt_render_passes in the order of YRT_PASS_*, float4 per pixel in launch_render's layout;
+// only the planes whose bit is set in `mask` are written. beauty_rgba, when not null, receives
+// launch_render_wavefront's image from the same walk. Counters and timings as there.
+enum pass_index {
+    pass_direct = 0,
+    pass_diffuse = 1,
+    pass_specular = 2,
+    pass_reflection = 3,
+    pass_ambient = 4,
+    pass_count = 5
+};
+struct dev_pass_planes {
+    float* plane[pass_count];
+};
+hipError_t launch_render_wavefront_passes(device_scene& ds, const dev_render_args& args, unsigned mask,
+                                          const dev_pass_planes& out, void* beauty_rgba, unsigned long long* counters,
+                                          bool packet, hipStream_t stream);
+
 }  // namespace yrt
