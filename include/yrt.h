@@ -322,6 +322,29 @@ typedef struct yrt_pass_planes { float* plane[YRT_PASS_COUNT]; } yrt_pass_planes
 int yrt_render_passes(yrt_scene* ds, const yrt_render_params* p, unsigned mask, const yrt_pass_planes* out,
                       float* beauty /* may be NULL */, int mem, void* stream);
 
+/* ---- shade() for caller-supplied rays ----
+ * shade() (src/raytrace.cpp:88-211) for n caller rays. rays: n x {o.xyz, d.xyz, tmin, tmax}
+ * as yrt_trace_first; out: n x RGBA f32, out[k] = shade(rays[k]) = {c.xyz, 1}, {0,0,0,1} on a miss.
+ * The level-0 ray is used as given: o, d (not renormalised), tmin and tmax all reach the
+ * closest-hit query, and the view vector is normalize(ray.o - p) from that ray's own origin
+ * (raytrace.cpp:147,196), so a batch may mix origins freely (orthographic, fisheye or panoramic
+ * cameras, light probes). Mirror and shadow rays, the accumulation order and max_depth are
+ * yrt_render's: a batch of one camera's eval_camera rays gives that render's samples bit for bit.
+ * Of `p`, ambient, max_depth, algorithm and timing mean what they mean in yrt_render (the
+ * megakernel takes max_depth <= 16 on a reflective scene, else YRT_ERR_UNSUPPORTED); count_work
+ * = 1 is YRT_ERR_UNSUPPORTED; every other field is ignored. `mem` says where both `rays` and
+ * `out` live: host buffers make the call synchronous, device buffers (out 16-byte aligned) are
+ * stream-ordered; `out` may not overlap `rays`. A null handle, p, rays or out with n > 0, n < 0
+ * or a bad `mem` return YRT_ERR_INVALID_ARG before any device call; n == 0 returns YRT_OK, writes
+ * nothing and leaves the counters at zero. The tile-list mode and the LDS staging of the handle
+ * do not change the result: a batch builds no lists and stages nothing, and yrt_scene_tile_lists
+ * / yrt_scene_lds_staging report that. yrt_last_stats then gives rays = the reference's
+ * intersect_first + intersect_any calls for these n shade() calls, camera_samples = n, and
+ * shadow_rays, shadow_rays_culled and depth_truncated as after yrt_render; yrt_last_timings the
+ * level-0 closest hit under YRT_PHASE_PRIMARY and the other phases as in a render. */
+int yrt_shade_rays(yrt_scene* ds, const yrt_render_params* p, const float* rays, int n, float* out_rgba, int mem,
+                   void* stream);
+
 #ifdef __cplusplus
 }
 #endif

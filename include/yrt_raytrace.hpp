@@ -7,6 +7,7 @@
 //     auto hdr = yrt_cpp::raytrace(scn, {a, a, a}, res, s);     // raytrace,   src/raytrace.cpp:213
 //     yrt_cpp::save_hdr_or_ldr(out, hdr);                       // image.cpp:81
 //     yrt_cpp::intersect_first(scn, ray) / intersect_any(...)   // scene.h:236-237
+//     yrt_cpp::shade(scn, {a, a, a}, ray)                       // shade,      src/raytrace.cpp:88
 // image4f is the reference's framebuffer (image.h:8-17): width, height, row-major
 // pixels[j*width+i] of RGBA float. The render runs on the GPU; the scene is copied
 // to HBM on the first render/trace call and stays resident with the scene.
@@ -198,6 +199,24 @@ inline intersection3f intersect_first(const std::unique_ptr<scene>& scn, const r
 }
 inline bool intersect_any(const std::unique_ptr<scene>& scn, const ray3f& ray) {
     return intersect_any(scn, std::vector<ray3f>{ray})[0];
+}
+
+// batch shade (raytrace.cpp:88-211; the lights are the scene's): {c.xyz, 1} per ray,
+// {0, 0, 0, 1} on a miss
+inline std::vector<vec4f> shade(const std::unique_ptr<scene>& scn, const vec3f& amb, const std::vector<ray3f>& rays,
+                                int max_depth = 16) {
+    static_assert(sizeof(ray3f) == 8 * sizeof(float) && sizeof(vec4f) == 4 * sizeof(float), "ray3f / vec4f layout");
+    const int n = (int)rays.size();
+    std::vector<vec4f> out(n);
+    if (!n) return out;
+    yrt_render_params p = scn->params;
+    p.ambient[0] = amb.x, p.ambient[1] = amb.y, p.ambient[2] = amb.z;
+    p.max_depth = max_depth;
+    check(yrt_shade_rays(scn->on_device(), &p, &rays[0].o.x, n, &out[0].x, YRT_MEM_HOST, nullptr), "shade");
+    return out;
+}
+inline vec4f shade(const std::unique_ptr<scene>& scn, const vec3f& amb, const ray3f& ray) {
+    return shade(scn, amb, std::vector<ray3f>{ray})[0];
 }
 
 // save_hdr_or_ldr (src/image.cpp:81-88)

@@ -24,7 +24,7 @@ from ._native import RenderParams, Stats, YrtError, check
 
 __all__ = [
     "Scene", "DeviceScene", "load_scene", "build_bvh", "raytrace", "render_aovs", "render_passes", "intersect_first",
-    "intersect_any", "tonemap", "save_hdr_or_ldr", "render_params", "device_count", "YrtError",
+    "intersect_any", "shade_rays", "tonemap", "save_hdr_or_ldr", "render_params", "device_count", "YrtError",
 ]
 
 ALGORITHMS = {"wavefront": 0, "megakernel": 1, "wavefront_lane": 2}
@@ -247,6 +247,15 @@ class DeviceScene:
         mem = N.YRT_MEM_DEVICE if device_memory else N.YRT_MEM_HOST
         check(N.lib.yrt_render_passes(self._h, C.byref(params), mask, C.byref(pp), C.c_void_p(beauty_ptr or 0), mem,
                                       C.c_void_p(stream or 0)), "yrt_render_passes")
+
+    def shade_rays_into(self, params: RenderParams, rays_ptr: int, n: int, out_ptr: int, device_memory: bool = True,
+                        stream: Optional[int] = None) -> None:
+        """Launch shade() for n caller rays (yrt_shade_rays): `rays_ptr` n x 8 float32 {o.xyz,
+        d.xyz, tmin, tmax}, `out_ptr` n x RGBA float32, both device pointers by default, stream
+        ordered. Of `params`, ambient, max_depth, algorithm and timing are used."""
+        mem = N.YRT_MEM_DEVICE if device_memory else N.YRT_MEM_HOST
+        check(N.lib.yrt_shade_rays(self._h, C.byref(params), C.c_void_p(rays_ptr), int(n), C.c_void_p(out_ptr), mem,
+                                   C.c_void_p(stream or 0)), "yrt_shade_rays")
 
     def last_timings(self) -> dict:
         """per-phase GPU ms of the last render with timing=True: {phase: (ms, launches)}"""
@@ -497,6 +506,22 @@ def intersect_any(scn, rays) -> np.ndarray:
     check(N.lib.yrt_trace_any(ds.handle, r.ctypes.data, r.shape[0], hit.ctypes.data, N.YRT_MEM_HOST,
                               None), "intersect_any")
     return hit.astype(bool)
+
+
+def shade_rays(scn, rays, amb: Sequence[float] = (0.1, 0.1, 0.1), *, max_depth: int = 16,
+               algorithm: str = "wavefront", return_stats: bool = False):
+    """Batch shade (src/raytrace.cpp:88): the colour of each caller ray, (n, 4) float32 {c.xyz, 1},
+    {0, 0, 0, 1} on a miss. `rays` is (n, 8) {o.xyz, d.xyz, tmin, tmax}, used as given (d is not
+    renormalised; the view vector comes from each ray's own origin), so any camera model can be
+    written as a ray generator. `scn` is a Scene or a DeviceScene, as for raytrace."""
+    r = _rays_array(rays)
+    ds = _device_scene(scn)
+    p = render_params(amb, max_depth=max_depth, algorithm=algorithm)
+    out = np.zeros((r.shape[0], 4), np.float32)
+    ds.shade_rays_into(p, r.ctypes.data, r.shape[0], out.ctypes.data, device_memory=False)
+    if return_stats:
+        return out, ds.last_stats()
+    return out
 
 
 def tonemap(img: np.ndarray) -> np.ndarray:

@@ -155,6 +155,7 @@ _sig = {
     "yrt_render_multi": (C.c_int, [_vp, _ip, C.c_int, C.POINTER(RenderParams), _vp, C.c_int]),
     "yrt_render_aovs": (C.c_int, [_vp, C.POINTER(RenderParams), C.c_uint, C.POINTER(AovPlanes), C.c_int, _vp]),
     "yrt_render_passes": (C.c_int, [_vp, C.POINTER(RenderParams), C.c_uint, C.POINTER(PassPlanes), _vp, C.c_int, _vp]),
+    "yrt_shade_rays": (C.c_int, [_vp, C.POINTER(RenderParams), _vp, C.c_int, _vp, C.c_int, _vp]),
 }
 EXPORTS = tuple(_sig)
 

@@ -4,6 +4,7 @@
 #include <hip/hip_runtime_api.h>
 
 #include <cmath>
+#include <cstdint>
 #include <cstring>
 #include <mutex>
 #include <new>
@@ -734,6 +735,75 @@ int yrt_trace_first(yrt_scene* s, const float* rays, int n, unsigned char* hit, 
 
 int yrt_trace_any(yrt_scene* s, const float* rays, int n, unsigned char* hit, int mem, void* stream) {
     return trace_impl(s, rays, n, 1, hit, nullptr, nullptr, nullptr, nullptr, mem, stream);
+}
+
+int yrt_shade_rays(yrt_scene* s, const yrt_render_params* p, const float* rays, int n, float* out, int mem,
+                   void* stream) {
+    // (before any device call, and before the handle is looked at)
+    const char* bad = n < 0                                      ? "yrt_shade_rays: rays: n < 0"
+                      : mem != YRT_MEM_HOST && mem != YRT_MEM_DEVICE ? "yrt_shade_rays: rays: mem is not YRT_MEM_*"
+                      : n > 0 && !s                              ? "yrt_shade_rays: rays: null scene handle"
+                      : n > 0 && !p                              ? "yrt_shade_rays: rays: null params"
+                      : n > 0 && !rays                           ? "yrt_shade_rays: rays: null rays"
+                      : n > 0 && !out                            ? "yrt_shade_rays: rays: null out"
+                                                                 : nullptr;
+    if (!bad && n > 0) {
+        const char *r0 = (const char*)rays, *o0 = (const char*)out;
+        if (r0 < o0 + (size_t)n * 16 && o0 < r0 + (size_t)n * 32) bad = "yrt_shade_rays: out overlaps rays";
+        if (mem == YRT_MEM_DEVICE && ((uintptr_t)out & 15)) bad = "yrt_shade_rays: rays: a device out is 16-byte aligned";
+    }
+    if (bad) {
+        g_last_error = bad;
+        return YRT_ERR_INVALID_ARG;
+    }
+    if (!s) return YRT_OK;  // (n == 0 without a handle: nothing to do)
+    return guarded([&] {
+        hipStream_t st = (hipStream_t)stream;
+        hip_check(hipSetDevice(s->ds->device), "hipSetDevice");
+        if (n == 0) {  // nothing is written; the counters read zero
+            hip_check(hipMemsetAsync(s->counters, 0, yrt::cnt_slots * yrt::cnt_count * sizeof(unsigned long long), st),
+                      "hipMemsetAsync");
+            s->ds->timer.reset(false);
+            s->last_stream = st;
+            return YRT_OK;
+        }
+        if (p->algorithm != YRT_ALGO_MEGAKERNEL && p->algorithm != YRT_ALGO_WAVEFRONT &&
+            p->algorithm != YRT_ALGO_WAVEFRONT_LANE)
+            throw std::invalid_argument("unknown algorithm");
+        if (p->count_work != 0) throw yrt::unsupported_error("ray batches do not count work");
+        yrt::dev_render_args a = {};
+        for (int k = 0; k < 3; k++) a.amb[k] = p->ambient[k];
+        a.max_depth = p->max_depth > 0 ? p->max_depth : 16;
+        a.samples = 1;
+        if (p->algorithm == YRT_ALGO_MEGAKERNEL && s->ds->reflective && a.max_depth > yrt::megakernel_max_depth)
+            throw yrt::unsupported_error("the megakernel keeps " + std::to_string(yrt::megakernel_max_depth) +
+                                         " mirror levels per lane; deeper recursions need the wavefront algorithm");
+        const size_t rb = (size_t)n * 32, ob = (size_t)n * 16;
+        const float* d_rays = rays;
+        void* d_out = out;
+        if (mem != YRT_MEM_DEVICE) {  // a host batch is staged once
+            char* base = (char*)scratch(s, ((rb + 255) & ~(size_t)255) + ob);
+            hip_check(hipMemcpyAsync(base, rays, rb, hipMemcpyHostToDevice, st), "hipMemcpyAsync");
+            d_rays = (const float*)base;
+            d_out = base + ((rb + 255) & ~(size_t)255);
+        }
+        if (!(p->timing == 2 && s->ds->timer.on)) s->ds->timer.reset(p->timing != 0);
+        s->last_stream = st;
+        if (p->algorithm == YRT_ALGO_MEGAKERNEL) {
+            hip_check(hipMemsetAsync(s->counters, 0, yrt::cnt_slots * yrt::cnt_count * sizeof(unsigned long long), st),
+                      "hipMemsetAsync");
+            hip_check(yrt::launch_shade_rays(*s->ds, a, d_rays, n, d_out, s->counters, st), "shade_rays launch");
+        } else {
+            hip_check(yrt::launch_shade_rays_wavefront(*s->ds, a, d_rays, n, d_out, s->counters,
+                                                       p->algorithm == YRT_ALGO_WAVEFRONT, st),
+                      "wavefront shade_rays launch");
+        }
+        if (mem != YRT_MEM_DEVICE) {
+            hip_check(hipMemcpyAsync(out, d_out, ob, hipMemcpyDeviceToHost, st), "hipMemcpyAsync");
+            hip_check(hipStreamSynchronize(st), "hipStreamSynchronize");
+        }
+        return YRT_OK;
+    });
 }
 
 int yrt_last_stats(yrt_scene* s, yrt_stats* out) {

@@ -167,6 +167,28 @@ __global__ __launch_bounds__(BLOCK) void render_kernel(dev_scene_view S, dev_ren
     flush_counters<COUNT>(counters, L, samples);
 }
 
+// shade() (raytrace.cpp:88-211) for caller rays (yrt_shade_rays with the megakernel): one lane
+// = one ray, used as given (o, d, tmin, tmax reach the first closest-hit query; the view vector
+// is taken from the ray's own origin, shade_path's ray.o); out[k] = {c, 1}
+template <typename SE>
+__global__ __launch_bounds__(BLOCK) void shade_rays_kernel(dev_scene_view S, dev_render_args A,
+                                                           const float* __restrict__ rays, int n,
+                                                           float4* __restrict__ out, unsigned long long* counters) {
+    __shared__ SE lds[traversal_stack_cap * BLOCK];
+    lane_state<SE> L;
+    L.stk = lds + threadIdx.x;
+    const int k = blockIdx.x * BLOCK + threadIdx.x;
+    unsigned long long samples = 0;
+    if (k < n) {
+        const float* r = rays + (size_t)k * 8;
+        const ray3 ray = {{r[0], r[1], r[2]}, {r[3], r[4], r[5]}, r[6], r[7]};
+        const vec3f c = shade_path<false>(S, A, ray, L);
+        out[k] = make_float4(c.x, c.y, c.z, 1.0f);
+        samples = 1;
+    }
+    flush_counters<false>(counters, L, samples);
+}
+
 // batch intersect_first / intersect_any (scene.cpp:483-494), one lane per ray
 constexpr int TRACE_BLOCK = 256;
 template <bool ANY>
@@ -305,6 +327,21 @@ hipError_t launch_render(device_scene& ds, const dev_render_args& args, void* ou
             YRT_MK(false, uint32_t);
     }
 #undef YRT_MK
+    ds.timer.end(t, stream);
+    return hipGetLastError();
+}
+
+hipError_t launch_shade_rays(device_scene& ds, const dev_render_args& args, const float* rays, int n, void* out_rgba,
+                             unsigned long long* counters, hipStream_t stream) {
+    if (n <= 0) return hipSuccess;
+    const dim3 grid((n + BLOCK - 1) / BLOCK);
+    int t = ds.timer.begin(phase_megakernel, stream);
+    if (ds.narrow_stack)
+        hipLaunchKernelGGL(shade_rays_kernel<uint16_t>, grid, dim3(BLOCK), 0, stream, ds.view, args, rays, n,
+                           (float4*)out_rgba, counters);
+    else
+        hipLaunchKernelGGL(shade_rays_kernel<uint32_t>, grid, dim3(BLOCK), 0, stream, ds.view, args, rays, n,
+                           (float4*)out_rgba, counters);
     ds.timer.end(t, stream);
     return hipGetLastError();
 }

@@ -15,6 +15,9 @@
 //    k_shade; a sample whose value is final folds it up its chain of parents at once:
 //    R_k = (D_k + R_{k+1}*kr_k) + la_k)
 //   k_accumulate  the ordered per-pixel sum of raytrace.cpp:232-249
+// A ray batch (yrt_shade_rays, run_rays) is the same pipeline with its level 0 from the caller:
+// k_rays_first (the rays as given, the generic closest-hit walk), k_rays_shadow and k_rays_shade
+// (the view point per sample from the ray's own origin), then the levels above; one RGBA per ray.
 //
 // Why: every traversal kernel carries only its ray and stack (few VGPRs, high
 // occupancy), lanes of one wave are 64 samples of one pixel (s=8) or an 8x8 pixel
@@ -103,7 +106,13 @@ struct wf_buffers {
     int* count;             // level k >= 1, segment g: rays at count[(k * level_segments + g) * count_stride]
     int seg;                // slots per segment of a mirror level (seg_count)
     unsigned* queue;        // work counters of the persistent grids: shadow [0, 8) per XCD + [8] shared, primary [16, 24) + [24]
-    const f4* trel;         // instance-level spine records relative to the camera origin
+    // a render's instance-level spine records relative to the camera origin -- or, in ray mode
+    // (yrt_shade_rays, run_rays), where no kernel reads those: this chunk's rays in the
+    // caller's buffer, 8 floats {o.xyz, d.xyz, tmin, tmax} per sample
+    union {
+        const f4* trel;
+        const float* rays;
+    };
     int capacity;           // samples per chunk
     int nlevels;            // levels allocated
     int need_v;             // the scene has textures: the surface's v (surfv) is stored and read
@@ -918,6 +927,47 @@ __global__ __launch_bounds__(YRT_PRIMARY_SP_BLOCK, YRT_PRIMARY_WAVES) void k_pri
     flush_block<2, SPB>(counters, {cnt_rays, cnt_samples}, {mine, mine});
 }
 
+// ---- level 0 of a ray batch (yrt_shade_rays): the caller's rays instead of eval_camera ----
+// Sample idx of the chunk is ray idx of B.rays, used as given: o, d (not renormalised), tmin and
+// tmax all reach the closest-hit query, as shade() hands its ray to intersect_first
+// (raytrace.cpp:91). The rays share no origin, so the walk is the mirror levels' generic one
+// (k_bounce's: world-space records from the root, no camera-relative records, no camera lists),
+// and the hit and surface records go where k_primary stores them. A partial block's idle lanes
+// reach the walk as invalid lanes, as in k_bounce.
+// The level-0 view point (raytrace.cpp:147,196: normalize(ray.o - p)) is re-read from B.rays by
+// the kernels that need it (ray_origin): 12 of the 32 bytes k_rays_first has just streamed,
+// against a per-sample origin record that would cost 16 B of workspace per sample and one more
+// store here for the same loads there.
+__device__ __forceinline__ vec3f ray_origin(const wf_buffers& B, int idx) {
+    const float* r = B.rays + (size_t)idx * 8;
+    return {r[0], r[1], r[2]};
+}
+
+template <bool PACKET, typename SE>
+__global__ __launch_bounds__(WF_BLOCK, YRT_TRACE_WAVES) void k_rays_first(dev_scene_view S, int n, wf_buffers B,
+                                                                          unsigned long long* counters) {
+    __shared__ traversal_lds<PACKET, SE> lds;
+    auto T = make_tracer<false, false, PACKET, SE>(lds);
+    work_counts wc;
+    const int idx = blockIdx.x * WF_BLOCK + threadIdx.x;
+    const bool valid = idx < n;
+    ray3 ray = {{0, 0, 0}, {0, 0, 1}, ray_eps, flt_max};
+    if (valid) {
+        const float* r = B.rays + (size_t)idx * 8;
+        ray = {{r[0], r[1], r[2]}, {r[3], r[4], r[5]}, r[6], r[7]};
+    }
+    hit_record hr = {-1, -1, {0, 0, 0, 0}, 0};
+    const bool hit = T.trace(S, ray, valid, hr, wc);
+    if (valid) {
+        if (YRT_HIT16)
+            store_hit16(B, idx, hit, hr);
+        else
+            store_hit_surface(S, B, idx, hit, hr);
+    }
+    // one intersect_first and one level-0 shade() call per ray
+    flush_block<2>(counters, {cnt_rays, cnt_samples}, {valid ? 1ull : 0ull, valid ? 1ull : 0ull});
+}
+
 // ---- levels >= 1: closest hit of the compacted mirror rays (grid-stride) ----
 template <bool COUNT, bool PACKET, typename SE>
 __global__ __launch_bounds__(WF_BLOCK, YRT_TRACE_WAVES) void k_bounce(dev_scene_view S, int level, wf_buffers B,
@@ -1035,6 +1085,67 @@ __global__ __launch_bounds__(shadow_block<PACKET>(), YRT_SHADOW_WAVES) void k_sh
         flush(counters, cnt_shadow_prim_tests, wc.prim);
         flush(counters, cnt_shadow_wave_node_visits, wc.wnode);
     }
+}
+
+// level 0 of a ray batch (run_rays): k_shadow's level-0 work again -- the same grid (one block
+// per BS samples and light, the light index minor, dealt in XCD runs), shadow ray, cull and walk
+// -- with the view point of the zero-light-term cull taken per sample from the ray's own origin
+// (ray_origin) instead of the camera's. A kernel of its own, not a flag of k_shadow: the
+// render's kernels keep the code they have. Every lane of a partial block reaches the walk.
+template <bool PACKET, typename SE, bool WIDE>
+__global__ __launch_bounds__(shadow_block<PACKET>(), YRT_SHADOW_WAVES) void k_rays_shadow(dev_scene_view S, int nsamp,
+                                                                                          wf_buffers B,
+                                                                                          unsigned long long* counters) {
+    constexpr int BS = shadow_block<PACKET>();
+    __shared__ traversal_lds<PACKET, SE> lds;
+    auto T = make_tracer<true, false, PACKET, SE>(lds);
+    const unsigned lin = xcd_runs<YRT_SHADOW_LIGHT_MINOR>(blockIdx.y * gridDim.x + blockIdx.x, gridDim.x * gridDim.y);
+    const int li = (int)(lin % gridDim.y);
+    const int idx = (int)(lin / gridDim.y) * BS + (int)threadIdx.x;
+    const f4* lr = S.lights + 6 * li;
+    const frame3f lf = {xyz(ld4(lr)), xyz(ld4(lr + 1)), xyz(ld4(lr + 2)), xyz(ld4(lr + 3))};
+    const vec3f lp0 = xyz(ld4(lr + 4)), ke = xyz(ld4(lr + 5));
+    work_counts wc;
+    unsigned long long rays = 0, culled = 0;  // culled: counted in rays, answered without a walk
+    bool valid = false;
+    int info = -1;
+    float r = 1.0f;
+    float4 s1 = {0, 0, 0, 0};
+    vec3f ro = {0, 0, 0};
+    ray3 sr = {{0, 0, 0}, {0, 0, 1}, 0.01f, 1.0f};
+    constexpr bool CULL = YRT_SHADOW_CULL && !YRT_HIT16;
+    if (idx < nsamp) {
+        float4 s0 = ld4s(B.surf0 + idx);
+        if (CULL) {  // n and the view point, for light_term_zero
+            s1 = ld4s(B.surf1 + idx);
+            ro = ray_origin(B, idx);
+        }
+        info = sample_state(s0);
+        if (info >= 0) {
+            const vec3f p = YRT_HIT16 ? hit16_surface(S, s0).p : xyz(s0);
+            vec3f tp = transform_point(lf, lp0 - p);
+            vec3f l;
+            normalize_len(tp, l, r);
+            sr = {p, l, 0.01f, r - 0.01f};
+            valid = true;
+            rays++;
+        }
+    }
+    if (CULL) {  // (uniform control flow; a lane that is not a hit has info < 0)
+        if (light_term_zero(info, xyz(s1), sr.o, ro, sr.d, r, ke)) {
+            stb(B.occl + (size_t)li * B.capacity + idx, 1);
+            valid = false;
+            culled++;
+        }
+    }
+    hit_record hr;
+    bool occ;
+    if constexpr (WIDE)
+        occ = packet_occluded_wide2(S, sr, valid);
+    else
+        occ = T.trace(S, sr, valid, hr, wc);
+    if (valid) stb(B.occl + (size_t)li * B.capacity + idx, occ ? 1 : 0);
+    flush_block<2, BS>(counters, {cnt_shadow_rays, cnt_shadow_culled}, {rays, culled});
 }
 
 // The hull of box P = [P0, P1] and the point Lp, as the 16 lanes of a slot group hold it:
@@ -1902,10 +2013,14 @@ __global__ __launch_bounds__(SP_BLOCK, YRT_SHADOW_WAVES) void k_shadow_persist(d
 // registers per wave shorten them (A/B at c3: shade 1.55 -> 1.35 / 1.34 ms at 6 / 5 waves)
 #define YRT_SHADE_LEVEL_WAVES 5
 #endif
-template <bool COUNT, bool FUSE, int SB = WF_BLOCK, bool OCC4 = false>
-__global__ __launch_bounds__(SB, FUSE ? YRT_SHADE_WAVES : YRT_SHADE_LEVEL_WAVES) void k_shade(dev_scene_view S, dev_render_args A, int level, int nsamp_level0,
-                                                    int max_depth, wf_buffers B, unsigned long long* counters,
-                                                    chunk_args C, float4* __restrict__ out) {
+// RAYS (a ray batch, unfused, k_rays_shade): level 0's view point -- shading and the mirror-ray
+// spawn -- is the sample's own ray origin (ray_origin), and B.rad is the caller's output, one
+// RGBA per ray
+// (the kernels' body: k_shade and k_rays_shade keep their own names and launch bounds)
+template <bool COUNT, bool FUSE, int SB, bool OCC4, bool RAYS>
+__device__ __forceinline__ void shade_samples(dev_scene_view S, dev_render_args A, int level, int nsamp_level0,
+                                              int max_depth, wf_buffers B, unsigned long long* counters, chunk_args C,
+                                              float4* __restrict__ out) {
     __shared__ float4 fused_rad[FUSE ? SB : 1];
     __shared__ int cmp_count[SB / 64], cmp_base[SB / 64];
     __shared__ float srgb_lds[YRT_SHADE_LDS_SRGB ? 256 : 1];
@@ -1951,7 +2066,13 @@ __global__ __launch_bounds__(SB, FUSE ? YRT_SHADE_WAVES : YRT_SHADE_LEVEL_WAVES)
             bool write_r = info != -2;
             // level >= 1: this sample's ray record {origin, parent index}; with
             // YRT_FOLD_PREFETCH the parent's fold records are requested now
-            const float4 ro4 = (!FUSE && level) ? ld4(B.ray_o(level) + idx) : make_float4(cam_o.x, cam_o.y, cam_o.z, 0.0f);
+            float4 ro4 = (!FUSE && level) ? ld4(B.ray_o(level) + idx) : make_float4(cam_o.x, cam_o.y, cam_o.z, 0.0f);
+            if constexpr (RAYS && !FUSE) {
+                if (!level) {
+                    const vec3f o = ray_origin(B, idx);
+                    ro4 = make_float4(o.x, o.y, o.z, 0.0f);
+                }
+            }
             float4 pd = {0, 0, 0, 0}, pla = {0, 0, 0, 0}, pkr = {0, 0, 0, 0};
             if (YRT_FOLD_PREFETCH && !FUSE && level) {
                 const int parent = ibits(ro4.w);
@@ -2123,6 +2244,26 @@ __global__ __launch_bounds__(SB, FUSE ? YRT_SHADE_WAVES : YRT_SHADE_LEVEL_WAVES)
     }
     flush(counters, cnt_depth_truncated, truncated);
     if (COUNT) flush_work(counters, wc);
+}
+
+template <bool COUNT, bool FUSE, int SB = WF_BLOCK, bool OCC4 = false>
+__global__ __launch_bounds__(SB, FUSE ? YRT_SHADE_WAVES : YRT_SHADE_LEVEL_WAVES) void k_shade(dev_scene_view S, dev_render_args A, int level, int nsamp_level0,
+                                                    int max_depth, wf_buffers B, unsigned long long* counters,
+                                                    chunk_args C, float4* __restrict__ out) {
+    shade_samples<COUNT, FUSE, SB, OCC4, false>(S, A, level, nsamp_level0, max_depth, B, counters, C, out);
+}
+
+// every level of a ray batch (run_rays): the unfused k_shade; amb and max_depth are all it
+// reads of the render arguments
+template <bool OCC4>
+__global__ __launch_bounds__(WF_BLOCK, YRT_SHADE_LEVEL_WAVES) void k_rays_shade(dev_scene_view S, float3 amb3, int level,
+                                                                                int nsamp_level0, int max_depth,
+                                                                                wf_buffers B,
+                                                                                unsigned long long* counters) {
+    dev_render_args A = {};
+    A.amb[0] = amb3.x, A.amb[1] = amb3.y, A.amb[2] = amb3.z;
+    const chunk_args C = {0, nsamp_level0, 1, 1};
+    shade_samples<false, false, WF_BLOCK, OCC4, true>(S, A, level, nsamp_level0, max_depth, B, counters, C, nullptr);
 }
 
 // ---- ordered per-pixel sum (raytrace.cpp:232-249) ----
@@ -2838,7 +2979,155 @@ hipError_t run(device_scene& ds, const dev_render_args& A, float4* out, unsigned
     return hipGetLastError();
 }
 
+// ---- a ray batch (yrt_shade_rays): run()'s chunk loop with the caller's rays as level 0 ----
+// A ray is a sample and spp is 1: chunk r0 holds rays [r0, r0 + nsamp), its sample idx is ray
+// r0 + idx. k_rays_first replaces eval_camera and the camera-relative walk; level 0's shadow
+// rays run on the plain k_shadow grid (the persistent any-hit grid's item order and the
+// bundles' boxes are laid out for pixel tiles, and no camera list exists without a common
+// origin), so the tile-list mode and the LDS staging of the handle change nothing here and the
+// handle reports neither as used. The mirror levels, the fold and the workspace are run()'s;
+// the fold's last step writes the ray's colour straight into `out` (B.rad), in batch order.
+template <bool PACKET, typename SE>
+hipError_t run_rays(device_scene& ds, const dev_render_args& A, const float* rays, int n, float4* out,
+                    unsigned long long* counters, hipStream_t stream) {
+    constexpr int spp = 1;
+    const int nlevels = ds.reflective ? std::max(A.max_depth, 1) : 1;
+    long long target = 1ll << (ds.reflective ? MIRROR_CHUNK_LOG2 : CHUNK_LOG2);
+    auto rays_for = [&](long long tgt) { return (int)std::max<long long>(1, std::min<long long>(n, tgt)); };
+    // (run()'s slots per sample record: the mirror levels' segments and their slack)
+    auto seg_of = [&](int r) { return r / level_segments + level_segments * WF_BLOCK; };
+    auto cap_of = [&](int r) { return nlevels > 1 ? level_segments * seg_of(r) : r; };
+    auto bytes_of = [&](long long tgt) { return workspace_bytes(cap_of(rays_for(tgt)), spp, ds.nlights, nlevels); };
+    if (bytes_of(target) > ds.work_bytes) {  // (run()'s growth rule)
+        size_t free_b = 0, total_b = 0;
+        if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) free_b = 0;
+        free_b += ds.work_bytes;
+        while (target > (1ll << 16) && bytes_of(target) > free_b / 2) target /= 2;
+        if (bytes_of(target) > free_b)
+            throw unsupported_error("max_depth " + std::to_string(A.max_depth) + " needs " +
+                                    std::to_string(bytes_of(target) >> 20) + " MiB of mirror-level records for its " +
+                                    "smallest chunk; " + std::to_string(free_b >> 20) + " MiB of HBM are free");
+    }
+    const int per_chunk = rays_for(target);
+    const int seg = seg_of(per_chunk);
+    const int cap = cap_of(per_chunk);
+    const size_t need = workspace_bytes(cap, spp, ds.nlights, nlevels);
+    if (need > ds.work_bytes) {
+        if (ds.work) (void)hipFree(ds.work);
+        ds.work = nullptr;
+        ds.work_bytes = 0;
+        hipError_t e = hipMalloc(&ds.work, need);
+        if (e != hipSuccess) return e;
+        ds.work_bytes = need;
+    }
+    wf_buffers B = carve(ds.work, cap, spp, ds.nlights, nlevels);
+    B.seg = seg;
+    B.need_v = ds.view.ntextures > 0;
+    ds.last_camera_lists = ds.last_bundles = false;
+    ds.last_lds_staging = 0;
+    if (nlevels > 1 && !ds.level_count_host) {
+        hipError_t e = hipHostMalloc((void**)&ds.level_count_host, sizeof(int) * level_segments * count_stride,
+                                     hipHostMallocDefault);
+        if (e != hipSuccess) return e;
+    }
+    if (nlevels > 1 && !ds.level_count_ev) {
+        hipError_t e = hipEventCreateWithFlags(&ds.level_count_ev, hipEventDisableTiming);
+        if (e != hipSuccess) return e;
+    }
+    phase_timer& T = ds.timer;
+    const float4 cam4 = make_float4(0.0f, 0.0f, 0.0f, 0.0f);  // (no level takes its view point from a camera)
+    const int stride_grid = 2048;
+    constexpr int TB = shadow_block<PACKET>();
+    const bool wide = PACKET && ds.wide_ok;
+    const bool occ4 = ds.nlights <= 4;
+    const float3 amb3 = make_float3(A.amb[0], A.amb[1], A.amb[2]);
+    for (long long r0 = 0; r0 < n; r0 += per_chunk) {
+        const int nsamp = (int)std::min<long long>(per_chunk, n - r0);
+        const int grid = (nsamp + WF_BLOCK - 1) / WF_BLOCK;
+        const int tgrid = (nsamp + TB - 1) / TB;
+        B.rays = rays + (size_t)r0 * 8;
+        B.rad = reinterpret_cast<f4*>(out + r0);
+        int t = T.begin(phase_lists, stream);
+        {
+            // the chunk's zeroed counters (k_chunk_setup without the camera-relative records)
+            const int count_ints = nlevels > 1 ? (int)(count_bytes(nlevels) / sizeof(int)) : 0;
+            const int counter_words = r0 == 0 && counters ? cnt_slots * cnt_count : 0;
+            const int work = std::max(std::max(count_ints, counter_words), 32);
+            const int nb = std::min((work + WF_BLOCK - 1) / WF_BLOCK, 1024);
+            hipLaunchKernelGGL(k_chunk_setup, dim3(nb), dim3(WF_BLOCK), 0, stream, (const f4*)nullptr, 0, 0.0f, 0.0f,
+                               0.0f, ds.trel, B.queue, (unsigned long long*)nullptr, B.count, count_ints, counters,
+                               counter_words);
+        }
+        T.end(t, stream);
+        t = T.begin(phase_primary, stream);
+        hipLaunchKernelGGL((k_rays_first<PACKET, SE>), dim3(grid), dim3(WF_BLOCK), 0, stream, ds.view, nsamp, B,
+                           counters);
+        T.end(t, stream);
+        for (int level = 0; level < nlevels; level++) {  // (run()'s level loop)
+            if (level > 0) {
+                t = T.begin(phase_bounce, stream);
+                hipLaunchKernelGGL((k_bounce<false, PACKET, SE>), dim3(stride_grid), dim3(WF_BLOCK), 0, stream, ds.view,
+                                   level, B, counters);
+                T.end(t, stream);
+                hipError_t e = hipEventSynchronize(ds.level_count_ev);
+                if (e != hipSuccess) return e;
+                bool any = false;
+                for (int g = 0; g < level_segments; g++) any |= ds.level_count_host[g * count_stride] != 0;
+                if (!any) break;
+            }
+            if (ds.nlights > 0) {
+                const dim3 sg(level ? stride_grid * WF_BLOCK / TB : tgrid, ds.nlights);
+                t = T.begin(phase_shadow, stream);
+                if constexpr (PACKET) {
+                    if (wide && level)
+                        hipLaunchKernelGGL((k_shadow<false, true, SE, true>), sg, dim3(TB), 0, stream, ds.view, level,
+                                           nsamp, B, counters, cam4);
+                    else if (wide)
+                        hipLaunchKernelGGL((k_rays_shadow<true, SE, true>), sg, dim3(TB), 0, stream, ds.view, nsamp, B,
+                                           counters);
+                }
+                if (!wide && level)
+                    hipLaunchKernelGGL((k_shadow<false, PACKET, SE, false>), sg, dim3(TB), 0, stream, ds.view, level,
+                                       nsamp, B, counters, cam4);
+                else if (!wide)
+                    hipLaunchKernelGGL((k_rays_shadow<PACKET, SE, false>), sg, dim3(TB), 0, stream, ds.view, nsamp, B,
+                                       counters);
+                T.end(t, stream);
+            }
+            t = T.begin(phase_shade, stream);
+            const dim3 hg(level ? stride_grid : grid);
+            if (occ4)
+                hipLaunchKernelGGL(k_rays_shade<true>, hg, dim3(WF_BLOCK), 0, stream, ds.view, amb3, level, nsamp,
+                                   A.max_depth, B, counters);
+            else
+                hipLaunchKernelGGL(k_rays_shade<false>, hg, dim3(WF_BLOCK), 0, stream, ds.view, amb3, level, nsamp,
+                                   A.max_depth, B, counters);
+            T.end(t, stream);
+            if (level + 1 < nlevels) {
+                hipError_t e = hipMemcpyAsync(ds.level_count_host,
+                                              B.count + (size_t)(level + 1) * level_segments * count_stride,
+                                              sizeof(int) * level_segments * count_stride, hipMemcpyDeviceToHost,
+                                              stream);
+                if (e == hipSuccess) e = hipEventRecord(ds.level_count_ev, stream);
+                if (e != hipSuccess) return e;
+            }
+        }
+    }
+    return hipGetLastError();
+}
+
 }  // namespace
+
+hipError_t launch_shade_rays_wavefront(device_scene& ds, const dev_render_args& args, const float* rays, int n,
+                                       void* out_rgba, unsigned long long* counters, bool packet, hipStream_t stream) {
+    if (n <= 0)  // (no chunk, so no k_chunk_setup: the counters still start at 0)
+        return counters ? hipMemsetAsync(counters, 0, (size_t)cnt_slots * cnt_count * sizeof(unsigned long long), stream)
+                        : hipSuccess;
+    float4* out = (float4*)out_rgba;
+    if (packet) return run_rays<true, uint32_t>(ds, args, rays, n, out, counters, stream);
+    if (ds.narrow_stack) return run_rays<false, uint16_t>(ds, args, rays, n, out, counters, stream);
+    return run_rays<false, uint32_t>(ds, args, rays, n, out, counters, stream);
+}
 
 hipError_t launch_render_wavefront(device_scene& ds, const dev_render_args& args, void* out_rgba,
                                    unsigned long long* counters, bool count_work, bool packet, hipStream_t stream) {

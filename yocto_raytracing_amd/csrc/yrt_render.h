@@ -15,7 +15,7 @@ namespace yrt {
 // per-phase GPU time of the last render call: HIP events recorded on the launch
 // stream around every kernel launch of a phase (enabled by yrt_render_params.timing)
 enum render_phase {
-    phase_primary = 0,   // camera rays + closest hit + surface (k_primary)
+    phase_primary = 0,   // camera rays + closest hit + surface (k_primary); a ray batch's level 0 (k_rays_first)
     phase_shadow = 1,    // shadow rays, any hit (k_shadow)
     phase_shade = 2,     // lighting + mirror-ray compaction (k_shade)
     phase_bounce = 3,    // closest hit of mirror rays (k_bounce)
@@ -139,6 +139,17 @@ constexpr int traversal_stack_cap = 40;
 // wavefront pipeline (wavefront.hip): same contract as launch_render
 hipError_t launch_render_wavefront(device_scene& ds, const dev_render_args& args, void* out_rgba,
                                    unsigned long long* counters, bool count_work, bool packet, hipStream_t stream);
+
+// shade() (raytrace.cpp:88-211) for n caller rays (yrt_shade_rays): rays n x {o.xyz, d.xyz,
+// tmin, tmax} and out n x RGBA f32, both device pointers; args carries amb and max_depth only.
+// The wavefront pipeline in ray mode (wavefront.hip run_rays: k_rays_first as level 0, then the
+// render's levels; counters zeroed in its first kernel, timings per phase) ...
+hipError_t launch_shade_rays_wavefront(device_scene& ds, const dev_render_args& args, const float* rays, int n,
+                                       void* out_rgba, unsigned long long* counters, bool packet, hipStream_t stream);
+// ... or one lane per ray through the megakernel's shade_path (render.hip; the caller zeroes
+// the counters and caps max_depth at megakernel_max_depth)
+hipError_t launch_shade_rays(device_scene& ds, const dev_render_args& args, const float* rays, int n, void* out_rgba,
+                             unsigned long long* counters, hipStream_t stream);
 
 // the shading passes (wavefront.hip k_shade_passes / k_accumulate_passes): the planes of
 // yrt_render_passes in the order of YRT_PASS_*, float4 per pixel in launch_render's layout;
