@@ -177,24 +177,31 @@ __device__ __forceinline__ void flush(unsigned long long* counters, int idx, uns
 // the timed kernels' counters: wave sums combined per block in LDS, then ONE device
 // atomic per counter per block into the block's counter line (a per-wave atomic
 // costs ~4x as many fabric atomics; the c4 shadow pass has 1.5 M blocks)
-template <int N, int BS = WF_BLOCK>
-__device__ __forceinline__ void flush_block(unsigned long long* counters, const int (&idx)[N],
-                                            const unsigned long long (&v)[N]) {
+// (tid: the thread's index in its block, threadIdx.x however the caller has it; index_of(k):
+// the counter of v[k])
+template <int N, int BS, class F>
+__device__ __forceinline__ void flush_block_at(unsigned long long* counters, const unsigned long long (&v)[N],
+                                               unsigned tid, F index_of) {
     __shared__ unsigned long long part[BS / 64][N];
-    const int w = threadIdx.x >> 6;
+    const int w = tid >> 6;
 #pragma unroll
     for (int k = 0; k < N; k++) {
         const unsigned long long s = wave_sum(v[k]);
-        if ((threadIdx.x & 63) == 0) part[w][k] = s;
+        if ((tid & 63) == 0) part[w][k] = s;
     }
     __syncthreads();
-    if (threadIdx.x < N) {
+    if (tid < N) {
         unsigned long long t = 0;
 #pragma unroll
-        for (int q = 0; q < BS / 64; q++) t += part[q][threadIdx.x];
+        for (int q = 0; q < BS / 64; q++) t += part[q][tid];
         const unsigned b = (blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x;
-        if (t) atomicAdd(counters + (size_t)(b % cnt_slots) * cnt_count + idx[threadIdx.x], t);
+        if (t) atomicAdd(counters + (size_t)(b % cnt_slots) * cnt_count + index_of(tid), t);
     }
+}
+template <int N, int BS = WF_BLOCK>
+__device__ __forceinline__ void flush_block(unsigned long long* counters, const int (&idx)[N],
+                                            const unsigned long long (&v)[N]) {
+    flush_block_at<N, BS>(counters, v, threadIdx.x, [&](unsigned k) { return idx[k]; });
 }
 
 __device__ __forceinline__ void flush_work(unsigned long long* counters, const work_counts& wc) {
@@ -1877,6 +1884,72 @@ __global__ __launch_bounds__(256) void k_list_stats(wf_buffers B, int ntiles, in
 #define YRT_SHADOW_LDS_RECORDS 85
 #endif
 
+// one light of a 64-sample item of k_shadow_shade_persist: the shadow ray of lane's sample
+// idx = bx * 64 + lane towards light li, and whether it is occluded (a culled ray counts as
+// occluded). valid: the lane has a ray. This is k_shadow_persist's light loop body as a
+// function; k_shadow_persist keeps its own text: its kept variants (YRT_HIT16=1,
+// YRT_SHADOW_CULL=0) do not compile through the function ("invalid operand" in the walk's asm).
+// WCULL: `culled` counts the wave's culled rays (wave-uniform) instead of the lane's
+template <int LDSN, bool IL, bool WCULL = false>
+__device__ __forceinline__ bool shadow_item_light(const dev_scene_view& S, const wf_buffers& B, int nsamp, int bx,
+                                                  int li, int nl, unsigned lane, const vec3f& cam_o,
+                                                  const float4* lds_nodes, unsigned& rays, unsigned& culled_n,
+                                                  bool& valid) {
+    // the light's frame and position: one wave-uniform record, through the scalar cache
+    float4 lrec[6];
+    ld_records_at<6>(S.lights, (unsigned)(6 * li), lrec);
+    const frame3f lf = {xyz(lrec[0]), xyz(lrec[1]), xyz(lrec[2]), xyz(lrec[3])};
+    const vec3f lp0 = xyz(lrec[4]);
+    const int idx = bx * 64 + (int)lane;
+    valid = false;
+    int info = -1;
+    float r = 1.0f;
+    float4 s1 = {0, 0, 0, 0};
+    ray3 sr = {{0, 0, 0}, {0, 0, 1}, 0.01f, 1.0f};
+    if (idx < nsamp) {
+        // (every light of the item reads the sample's surface again: cached loads, not the
+        // streaming ones; holding it across the walks instead spills 5 VGPRs: +0.5 %)
+        float4 s0 = IL ? ld4(B.surf0 + idx) : ld4s(B.surf0 + idx);
+        if (YRT_SHADOW_CULL && !YRT_HIT16) s1 = IL ? ld4(B.surf1 + idx) : ld4s(B.surf1 + idx);  // n, for light_term_zero
+        info = sample_state(s0);
+        if (info >= 0) {
+            const vec3f p = YRT_HIT16 ? hit16_surface(S, s0).p : xyz(s0);
+            vec3f tp = transform_point(lf, lp0 - p);
+            vec3f l;
+            normalize_len(tp, l, r);
+            sr = {p, l, 0.01f, r - 0.01f};
+            valid = true;
+        }
+    }
+    rays += (unsigned)__popcll(ballot(valid));
+    // the rays whose light term is zero (light_term_zero, called by every lane in uniform
+    // control flow: its loads and ballots see the whole wave; it is false on a lane that is
+    // not a hit, info < 0, so it implies valid) start the walk as done -- recorded as
+    // occluded -- and a wave whose every ray is culled skips it. (Taking them out of `valid`
+    // instead trips the compiler inside this loop: "illegal VGPR to SGPR copy".)
+    const bool zero_term =
+        YRT_SHADOW_CULL && !YRT_HIT16 && light_term_zero(info, xyz(s1), sr.o, cam_o, sr.d, r, xyz(lrec[5]));
+    const unsigned long long culled = ballot(zero_term);
+    culled_n += WCULL ? (unsigned)__popcll(culled) : zero_term ? 1u : 0u;
+    const bool all_culled = YRT_SHADOW_CULL && !YRT_HIT16 && culled == ballot(valid);
+    int lc = -1;  // the bundle's list: its leaf count, -1 = walk the tree
+    if (YRT_SHADOW_BUNDLES && LDSN == 0 && B.bundles) {
+        const int gl = (bx / bundle_g) * nl + li;
+        lc = __builtin_amdgcn_readfirstlane(B.lcount[gl]);
+    }
+    const f4* tbase = S.wnodes;
+    uint32_t troot = (uint32_t)S.wtop_root;
+    if (lc > 0) {  // (the host turns bundles off with LDS-staged records: LDSN == 0 here)
+        tbase = B.lists;
+        troot = (uint32_t)(((bx / bundle_g) * nl + li) * bundle_recs * wide_record_bytes);
+    }
+    // lc == 0: no leaf can be passed by these rays, none is occluded; all_culled: recorded
+    // as occluded, k_shade skips the light
+    return all_culled ? true
+                     : lc == 0 ? ((culled >> lane) & 1ull) != 0
+                               : packet_occluded_wide2<LDSN, true>(S, sr, valid, lds_nodes, tbase, troot, culled);
+}
+
 template <int LDSN>
 __global__ __launch_bounds__(SP_BLOCK, YRT_SHADOW_WAVES) void k_shadow_persist(dev_scene_view S, int nsamp,
                                                                                 int nx, wf_buffers B,
@@ -2013,6 +2086,154 @@ __global__ __launch_bounds__(SP_BLOCK, YRT_SHADOW_WAVES) void k_shadow_persist(d
 // registers per wave shorten them (A/B at c3: shade 1.55 -> 1.35 / 1.34 ms at 6 / 5 waves)
 #define YRT_SHADE_LEVEL_WAVES 5
 #endif
+// shade() for one sample that hit (info >= 0), raytrace.cpp:99-206: the surface rows, the
+// material, the textures, the lights that are not occluded, the mirror branch. Every kernel
+// that shades calls this one body (k_shade, k_rays_shade and k_shadow_shade_persist's epilogue):
+// the image is bit-exact because they run the same operations in the same order.
+// OCC4: the lights' occlusion is the mask occ_bits, else the bytes B.occl.
+// LATE (k_shadow_shade_persist, at the any-hit grid's 64 VGPRs): what only the end needs, la and
+// kr and the reflective flag, is computed or loaded again after the light loop instead of held
+// across it; the same operations on the same values, 7 VGPR spills fewer.
+__device__ __forceinline__ vec3f amb_of(const vec3f& a) { return a; }
+__device__ __forceinline__ vec3f amb_of(const float* a) { return {a[0], a[1], a[2]}; }  // (LATE: read where it is used)
+template <bool COUNT, bool FUSE, bool OCC4, bool LATE = false, class AMB = vec3f>
+__device__ __forceinline__ void shade_hit(const dev_scene_view& S, const wf_buffers& B, int idx, int info,
+                                          const float4& s0, const float4& ro4, uint32_t occ_bits, int level,
+                                          int max_depth, const AMB& amb, const float* lut, work_counts& wc,
+                                          unsigned long long& truncated, vec3f& R, vec3f& p, bool& spawn, vec3f& dr,
+                                          vec3f& rec_d, vec3f& rec_la, int& rec_mat, bool& write_r) {
+    vec3f nrm;
+    vec2f uv;
+    int mat, kind;
+    if (YRT_HIT16) {
+        const surface sf = hit16_surface(S, s0);
+        p = sf.p, nrm = sf.n, uv = sf.uv, mat = sf.mat, kind = sf.kind;
+    } else {
+        const float4 s1 = ld4s(B.surf1 + idx);
+        p = xyz(s0), nrm = xyz(s1), uv = {s1.w, (!YRT_SKIP_UNUSED_V || B.need_v) ? lds1(B.surfv + idx) : 0.0f};
+        mat = info_mat(info), kind = info & 3;
+    }
+    const vec3f ro = xyz(ro4);
+    float4 m0, m1, m2, m3;
+    {
+        m0 = ld4(S.mats + 4 * mat), m1 = ld4(S.mats + 4 * mat + 1);
+        m2 = ld4(S.mats + 4 * mat + 2), m3 = ld4(S.mats + 4 * mat + 3);
+    }
+    const vec3f kd0 = xyz(m0), ks0 = xyz(m1);
+    vec3f kr = xyz(m2);
+    const float ns = m0.w;
+    const int kd_txt = ibits(m1.w), ks_txt = ibits(m2.w);
+    bool reflective = !LATE && (ibits(m3.w) & mat_reflective);
+    vec3f la = {0, 0, 0};
+    if (!LATE) la = amb_of(amb) * kd0;
+    vec3f tkd = {1, 1, 1}, tks = {1, 1, 1};
+    if (kd_txt >= 0) {
+        tkd = eval_texture<COUNT>(S, kd_txt, uv, wc, lut);
+        if (!LATE) la = la * tkd;
+    }
+    if (ks_txt >= 0) tks = eval_texture<COUNT>(S, ks_txt, uv, wc, lut);
+    vec3f c = {0.0f, 0.0f, 0.0f};
+    // raytrace.cpp:147 (per light) and :196 (mirror): the same value each time
+    vec3f v;
+    float vlen;
+    normalize_len(ro - p, v, vlen);
+    for (int li = 0; li < S.nlights; li++) {
+        if (OCC4 ? ((occ_bits >> li) & 1u) != 0u : ldb(B.occl + (size_t)li * B.capacity + idx) != 0) continue;
+        const f4* lr = S.lights + 6 * li;
+        // the light record is the same for every lane (li is the loop index):
+        // one scalar fetch instead of six 64-lane vector loads of one address
+        float4 lrec[6];
+        ld_scalar<6>(lr, lrec);
+        frame3f lf = {xyz(lrec[0]), xyz(lrec[1]), xyz(lrec[2]), xyz(lrec[3])};
+        vec3f lp0 = xyz(lrec[4]), ke = xyz(lrec[5]);
+        vec3f tp = transform_point(lf, lp0 - p);
+        vec3f l, h;
+        float r, hlen;
+        normalize_len(tp, l, r);
+        normalize_len(v + l, h, hlen);
+        vec3f kd = kd0, ks = ks0;
+        if (kd_txt >= 0) kd = kd * tkd;
+        if (ks_txt >= 0) ks = ks * tks;
+        const vec3f ker = div3(ke, r * r);
+        vec3f ld = kd * ker;
+        vec3f ls = ks * ker;
+        if (kind == kind_lines) {
+            float prodnl = dot(nrm, l);
+            float prodnh = dot(nrm, h);
+            if (prodnl < 0.0f) prodnl *= -1;
+            if (prodnh < 0.0f) prodnh *= -1;
+            float sinnl = __builtin_sqrtf(1.0f - prodnl);
+            float sinnh = __builtin_sqrtf(1.0f - prodnh);
+            ld = ld * sinnl;
+            ls = ls * spec_pow(sinnh, ns, ls);
+        } else {
+            ld = ld * smax(0.0f, dot(nrm, l));
+            ls = ls * spec_pow(smax(0.0f, dot(nrm, h)), ns, ls);
+        }
+        c = c + (ld + ls);
+    }
+    if (LATE) {
+        la = amb_of(amb) * kd0;
+        if (kd_txt >= 0) la = la * tkd;
+        // (the material's address from the sample's info again, not a pointer kept in registers)
+        int matl = info_mat(info);
+        asm volatile("" : "+v"(matl));
+        const f4* ml = S.mats + 4 * matl;
+        reflective = ibits(ld4(ml + 3).w) & mat_reflective;
+        if (reflective) kr = xyz(ld4(ml + 2));
+    }
+    if (!reflective) {
+        R = c + la;
+    } else if (FUSE || level + 1 >= max_depth || level + 1 >= B.nlevels) {
+        // (FUSE runs one-level renders: B.nlevels == 1, no mirror ray is spawned)
+        // depth cap: the reflected contribution counts as a miss (col = 0)
+        truncated++;
+        vec3f t = {0.0f * kr.x, 0.0f * kr.y, 0.0f * kr.z};
+        R = (c + t) + la;
+    } else {
+        spawn = true;
+        dr = (nrm * 2.0f * dot(nrm, v)) - v;
+        rec_d = c;
+        rec_la = la;
+        rec_mat = mat;
+        write_r = false;
+    }
+    if (COUNT) wc.hits++;
+}
+
+// the fused shapes' per-pixel sums: `ppb` pixels from chunk pixel pl0 on, their samples
+// consecutive in `rad` (LDS); lane t0 of STRIDE takes every STRIDE-th (pixel, component).
+// SPP: C.spp where the caller knows it at compile time (the chain of adds is unrolled, its
+// LDS reads issued ahead of it), else 0
+template <int STRIDE, int SPP = 0>
+__device__ __forceinline__ void sum_pixels(const dev_render_args& A, const chunk_args& C, float4* __restrict__ out,
+                                           const float4* rad, int pl0, int ppb, int t0) {
+    for (int t = t0; t < 3 * ppb; t += STRIDE) {
+        const int px = t / 3, comp = t - 3 * px;
+        const int pl = pl0 + px;
+        int lx, ly, i, j;
+        const bool valid = pl < C.npix && pixel_of(A, C.tiles_x, C.pix0 + pl, lx, ly, i, j);
+        if (pl < C.npix && lx < A.tile_w && ly < A.tile_h) {
+            float v = 0.0f;
+            if (valid) {
+                const int spp = SPP ? SPP : C.spp;
+                const float* r = reinterpret_cast<const float*>(rad + px * spp) + comp;
+                float acc = 0.0f;
+                if constexpr (SPP > 0) {
+#pragma unroll
+                    for (int q = 0; q < SPP; q++) acc = acc + r[4 * q];
+                } else {
+                    for (int q = 0; q < spp; q++) acc = acc + r[4 * q];
+                }
+                v = acc / float(spp);
+            }
+            float* o = reinterpret_cast<float*>(out + (size_t)ly * A.out_stride + lx);
+            o[comp] = v;
+            if (comp == 0) o[3] = valid ? 1.0f : 0.0f;
+        }
+    }
+}
+
 // RAYS (a ray batch, unfused, k_rays_shade): level 0's view point -- shading and the mirror-ray
 // spawn -- is the sample's own ray origin (ray_origin), and B.rad is the caller's output, one
 // RGBA per ray
@@ -2080,91 +2301,8 @@ __device__ __forceinline__ void shade_samples(dev_scene_view S, dev_render_args 
                 pkr = ld4(S.mats + 4 * ibits(pd.w) + 2);
             }
             if (info >= 0) {
-                vec3f nrm;
-                vec2f uv;
-                int mat, kind;
-                if (YRT_HIT16) {
-                    const surface sf = hit16_surface(S, s0);
-                    p = sf.p, nrm = sf.n, uv = sf.uv, mat = sf.mat, kind = sf.kind;
-                } else {
-                    const float4 s1 = ld4s(B.surf1 + idx);
-                    p = xyz(s0), nrm = xyz(s1), uv = {s1.w, (!YRT_SKIP_UNUSED_V || B.need_v) ? lds1(B.surfv + idx) : 0.0f};
-                    mat = info_mat(info), kind = info & 3;
-                }
-                const vec3f ro = xyz(ro4);
-                float4 m0, m1, m2, m3;
-                {
-                    m0 = ld4(S.mats + 4 * mat), m1 = ld4(S.mats + 4 * mat + 1);
-                    m2 = ld4(S.mats + 4 * mat + 2), m3 = ld4(S.mats + 4 * mat + 3);
-                }
-                const vec3f kd0 = xyz(m0), ks0 = xyz(m1), kr = xyz(m2);
-                const float ns = m0.w;
-                const int kd_txt = ibits(m1.w), ks_txt = ibits(m2.w);
-                const bool reflective = ibits(m3.w) & mat_reflective;
-                vec3f la = amb * kd0;
-                vec3f tkd = {1, 1, 1}, tks = {1, 1, 1};
-                if (kd_txt >= 0) {
-                    tkd = eval_texture<COUNT>(S, kd_txt, uv, wc, lut);
-                    la = la * tkd;
-                }
-                if (ks_txt >= 0) tks = eval_texture<COUNT>(S, ks_txt, uv, wc, lut);
-                vec3f c = {0.0f, 0.0f, 0.0f};
-                // raytrace.cpp:147 (per light) and :196 (mirror): the same value each time
-                vec3f v;
-                float vlen;
-                normalize_len(ro - p, v, vlen);
-                for (int li = 0; li < S.nlights; li++) {
-                    if (OCC4 ? ((occ_bits >> li) & 1u) != 0u : ldb(B.occl + (size_t)li * B.capacity + idx) != 0) continue;
-                    const f4* lr = S.lights + 6 * li;
-                    // the light record is the same for every lane (li is the loop index):
-                    // one scalar fetch instead of six 64-lane vector loads of one address
-                    float4 lrec[6];
-                    ld_scalar<6>(lr, lrec);
-                    frame3f lf = {xyz(lrec[0]), xyz(lrec[1]), xyz(lrec[2]), xyz(lrec[3])};
-                    vec3f lp0 = xyz(lrec[4]), ke = xyz(lrec[5]);
-                    vec3f tp = transform_point(lf, lp0 - p);
-                    vec3f l, h;
-                    float r, hlen;
-                    normalize_len(tp, l, r);
-                    normalize_len(v + l, h, hlen);
-                    vec3f kd = kd0, ks = ks0;
-                    if (kd_txt >= 0) kd = kd * tkd;
-                    if (ks_txt >= 0) ks = ks * tks;
-                    const vec3f ker = div3(ke, r * r);
-                    vec3f ld = kd * ker;
-                    vec3f ls = ks * ker;
-                    if (kind == kind_lines) {
-                        float prodnl = dot(nrm, l);
-                        float prodnh = dot(nrm, h);
-                        if (prodnl < 0.0f) prodnl *= -1;
-                        if (prodnh < 0.0f) prodnh *= -1;
-                        float sinnl = __builtin_sqrtf(1.0f - prodnl);
-                        float sinnh = __builtin_sqrtf(1.0f - prodnh);
-                        ld = ld * sinnl;
-                        ls = ls * spec_pow(sinnh, ns, ls);
-                    } else {
-                        ld = ld * smax(0.0f, dot(nrm, l));
-                        ls = ls * spec_pow(smax(0.0f, dot(nrm, h)), ns, ls);
-                    }
-                    c = c + (ld + ls);
-                }
-                if (!reflective) {
-                    R = c + la;
-                } else if (FUSE || level + 1 >= max_depth || level + 1 >= B.nlevels) {
-                    // (FUSE runs one-level renders: B.nlevels == 1, no mirror ray is spawned)
-                    // depth cap: the reflected contribution counts as a miss (col = 0)
-                    truncated++;
-                    vec3f t = {0.0f * kr.x, 0.0f * kr.y, 0.0f * kr.z};
-                    R = (c + t) + la;
-                } else {
-                    spawn = true;
-                    dr = (nrm * 2.0f * dot(nrm, v)) - v;
-                    rec_d = c;
-                    rec_la = la;
-                    rec_mat = mat;
-                    write_r = false;
-                }
-                if (COUNT) wc.hits++;
+                shade_hit<COUNT, FUSE, OCC4>(S, B, idx, info, s0, ro4, occ_bits, level, max_depth, amb, lut, wc,
+                                             truncated, R, p, spawn, dr, rec_d, rec_la, rec_mat, write_r);
             }
             if (FUSE) {
                 fused_rad[threadIdx.x] = make_float4(R.x, R.y, R.z, 1.0f);
@@ -2223,24 +2361,7 @@ __device__ __forceinline__ void shade_samples(dev_scene_view S, dev_render_args 
         // one lane per (pixel, colour component): each lane's sum is the reference's ordered
         // chain of adds (raytrace.cpp:232-249) for that component, so a pixel's three
         // dependent chains run side by side (A/B: c4 shade 2.00 -> 1.96 ms)
-        for (int t = (int)threadIdx.x; t < 3 * ppb; t += SB) {
-            const int px = t / 3, comp = t - 3 * px;
-            const int pl = (int)(blockIdx.x * SB / C.spp) + px;
-            int lx, ly, i, j;
-            const bool valid = pl < C.npix && pixel_of(A, C.tiles_x, C.pix0 + pl, lx, ly, i, j);
-            if (pl < C.npix && lx < A.tile_w && ly < A.tile_h) {
-                float v = 0.0f;
-                if (valid) {
-                    const float* r = reinterpret_cast<const float*>(fused_rad + px * C.spp) + comp;
-                    float acc = 0.0f;
-                    for (int q = 0; q < C.spp; q++) acc = acc + r[4 * q];
-                    v = acc / float(C.spp);
-                }
-                float* o = reinterpret_cast<float*>(out + (size_t)ly * A.out_stride + lx);
-                o[comp] = v;
-                if (comp == 0) o[3] = valid ? 1.0f : 0.0f;
-            }
-        }
+        sum_pixels<SB>(A, C, out, fused_rad, (int)(blockIdx.x * SB / C.spp), ppb, (int)threadIdx.x);
     }
     flush(counters, cnt_depth_truncated, truncated);
     if (COUNT) flush_work(counters, wc);
@@ -2265,6 +2386,135 @@ __global__ __launch_bounds__(WF_BLOCK, YRT_SHADE_LEVEL_WAVES) void k_rays_shade(
     const chunk_args C = {0, nsamp_level0, 1, 1};
     shade_samples<false, false, WF_BLOCK, OCC4, true>(S, A, level, nsamp_level0, max_depth, B, counters, C, nullptr);
 }
+
+// ---- level 0's shadow rays and shading in one persistent grid ----
+#if !defined(YRT_SHADOW_SHADE_FUSE)  // (its non-default build is the `unfused` library of tools/build_variants.py)
+// one level, 1 / 4 / 16 / 64 spp, at most 32 lights: an item of the any-hit grid (a 64-sample
+// block with all its lights, YRT_SHADOW_ITEM_LIGHTS) is whole pixels in one wave, which knows
+// every light's answer when the item ends. The wave shades and sums its pixels at once
+// (k_shadow_shade_persist) instead of writing occlusion bytes for a k_shade launch to read back
+// (A/B, one process, shadow + shade: c4 9.29 -> 9.02 ms, instance1k 6.37 -> 6.11, instance100k
+// 4.89 -> 4.60, rank 0 of 8 1.28 -> 1.23; with the 64-spp sum not unrolled c4 was 9.31)
+#define YRT_SHADOW_SHADE_FUSE 1
+#endif
+// (built with the item-lights grid, the cull and the default surface rows: the kept variants
+// without them -- YRT_SHADOW_ITEM_LIGHTS=0, YRT_SHADOW_CULL=0, YRT_HIT16=1 -- keep the two kernels)
+#if (YRT_SHADOW_SHADE_FUSE && YRT_SHADOW_ITEM_LIGHTS && YRT_SHADOW_CULL && !YRT_HIT16)
+#define YRT_SHADOW_SHADE_KERNEL 1
+#else
+#define YRT_SHADOW_SHADE_KERNEL 0
+#endif
+#if (YRT_SHADOW_SHADE_KERNEL)
+// k_shadow_persist<0>'s item loop with the answers kept as one bit per light and lane, then
+// per item k_shade<fused>'s body: shade_hit for the lane's sample, the 64 values through a
+// per-wave LDS slab, sum_pixels over the item's 64 / spp pixels. A wave does its own items:
+// no block barrier inside the loop.
+__global__ __launch_bounds__(SP_BLOCK, YRT_SHADOW_WAVES) void k_shadow_shade_persist(dev_scene_view S,
+                                                                                      dev_render_args A, int nsamp,
+                                                                                      int nx, wf_buffers B,
+                                                                                      unsigned long long* counters,
+                                                                                      chunk_args C,
+                                                                                      float4* __restrict__ out) {
+    constexpr int WPB = SP_BLOCK / 64;  // waves per block
+    constexpr unsigned RUN = YRT_SHADOW_ITEM_RUN;
+    __shared__ float4 wave_rad[WPB][64];
+    __shared__ unsigned wave_truncated[WPB];  // (in LDS: a register would be live across the walks)
+    __shared__ float srgb_lds[YRT_SHADE_LDS_SRGB ? 256 : 1];
+    // the epilogue reads the frame's and the chunk's arguments from an LDS copy, per item: as
+    // scalars they and what the compiler derives from them ahead of the loop (the reciprocals
+    // of the pixel enumeration's divisors, float(spp)) would be held across the walks
+    __shared__ struct {
+        dev_render_args A;
+        chunk_args C;
+    } args;
+    const float* lut = YRT_SHADE_LDS_SRGB ? srgb_lds : S.srgb;
+    if (YRT_SHADE_LDS_SRGB && S.ntextures > 0)  // uniform over the grid
+        for (int q = (int)threadIdx.x; q < 256; q += SP_BLOCK) srgb_lds[q] = S.srgb[q];
+    if (threadIdx.x == 0) args.A = A, args.C = C;
+    __syncthreads();
+    // (the view point as three scalars of their own, not as part of the four-dword kernel-argument
+    // load that brings it in: that tuple, live across the whole kernel, left an unused 16-byte
+    // spill slot, and with it a private segment, behind)
+    float cam_x = A.cam.ox, cam_y = A.cam.oy, cam_z = A.cam.oz;
+    asm volatile("" : "+s"(cam_x), "+s"(cam_y), "+s"(cam_z));
+    const vec3f cam_o = {cam_x, cam_y, cam_z};
+    const int nl = S.nlights;
+    __builtin_assume(nl > 0);  // (run() launches the any-hit grid for scenes with lights)
+    const unsigned n_items = (unsigned)nx;
+    // The lane index is taken again wherever it is needed, opaque to the compiler, and the
+    // wave index is a scalar: nothing derived from threadIdx.x is live across the walks. (With
+    // one `lane` for the kernel the compiler hoists what the epilogue derives from it -- the
+    // pixel, the component, the LDS addresses -- out of the item loop and spills it, 9 VGPRs.)
+    auto lane_now = []() {
+        unsigned l;
+        asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(l));
+        return l;
+    };
+    const int w = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const unsigned xcd = blockIdx.x % 8u;
+    // wave-uniform: this wave's shadow rays (the reference's count) and those answered without a walk
+    unsigned rays = 0, culled = 0;
+    if (lane_now() == 0) wave_truncated[w] = 0;
+    constexpr unsigned CS = YRT_SHADOW_BLOCK_CHUNK;
+    __shared__ chunk_ring ring;
+    const unsigned head = head_items<RUN, CS>(n_items);
+    chunk_ring_init<CS>(ring, B.queue + xcd, B.queue + 8, head / 8u);
+    for (;;) {
+        const unsigned q = chunk_ring_next<CS>(ring, B.queue + xcd, lane_now(), B.queue + 8, head / 8u);
+        const unsigned it = split_item<RUN>(q, xcd, n_items, head);
+        if (it >= n_items) break;
+        const int bx = (int)it;
+        uint32_t occ_bits = 0;  // bit li: light li is occluded for this lane's sample (or its term is zero)
+        for (int li = 0; li < nl; li++) {
+            bool valid;
+            const bool occ = shadow_item_light<0, true, true>(S, B, nsamp, bx, li, nl, lane_now(), cam_o, nullptr, rays,
+                                                              culled, valid);
+            occ_bits |= (occ ? 1u : 0u) << li;
+        }
+        // the item's samples are shaded (k_shade<fused>'s body for one sample) ...
+        const int idx = bx * 64 + (int)lane_now();
+        vec3f R = {0, 0, 0};
+        unsigned long long truncated = 0;
+        if (idx < nsamp) {
+            const float4 s0 = ld4(B.surf0 + idx);
+            const int info = sample_state(s0);
+            if (info >= 0) {
+                const float4 ro4 = make_float4(cam_o.x, cam_o.y, cam_o.z, 0.0f);
+                const float* amb = args.A.amb;
+                work_counts wc;
+                vec3f p = {0, 0, 0}, dr = {0, 0, 0}, rec_d = {0, 0, 0}, rec_la = {0, 0, 0};
+                int rec_mat = 0;
+                bool spawn = false, write_r = true;
+                shade_hit<false, true, true, true>(S, B, idx, info, s0, ro4, occ_bits, 0, 1, amb, lut, wc, truncated, R, p,
+                                             spawn, dr, rec_d, rec_la, rec_mat, write_r);
+            }
+        }
+        const unsigned lane = lane_now();
+        const unsigned ntrunc = (unsigned)__popcll(ballot(truncated != 0));
+        if (ntrunc && lane == 0) wave_truncated[w] += ntrunc;
+        // ... and its pixels summed from the wave's own slab: the wave's LDS operations complete
+        // in order, the waits keep the compiler from moving them across each other
+        wave_rad[w][lane] = make_float4(R.x, R.y, R.z, 1.0f);
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // every lane's value, before any lane sums
+        // (one pixel per item, 64 spp, is the long chain: 64 dependent adds per item)
+        const int spp = __builtin_amdgcn_readfirstlane(args.C.spp);
+        if (spp == 64) {
+            sum_pixels<64, 64>(args.A, args.C, out, wave_rad[w], bx, 1, (int)lane);
+        } else {
+            const int sl = __builtin_ctz((unsigned)spp);  // (spp divides 64: a power of two)
+            sum_pixels<64>(args.A, args.C, out, wave_rad[w], bx << (6 - sl), 64 >> sl, (int)lane);
+        }
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // the sums' reads, before the next item's values
+    }
+    const unsigned lane = lane_now();
+    const unsigned long long first = lane == 0 ? 1ull : 0ull;
+    // (the counters' indices as selects: a table of three indexed by a register takes a stack slot)
+    flush_block_at<3, SP_BLOCK>(
+        counters, {first * rays, first * culled, first * (lane == 0 ? wave_truncated[w] : 0u)},
+        (unsigned)w * 64u + lane,
+        [](unsigned k) { return k == 0 ? cnt_shadow_rays : k == 1 ? cnt_shadow_culled : cnt_depth_truncated; });
+}
+#endif
 
 // ---- ordered per-pixel sum (raytrace.cpp:232-249) ----
 // A wave sums 64 pixels. Their samples are consecutive in memory (spp per pixel), so the
@@ -2786,6 +3036,10 @@ hipError_t run(device_scene& ds, const dev_render_args& A, float4* out, unsigned
         const bool shadow_persist = !COUNT && PACKET && ds.wide_ok && TB == 64 && ds.nlights > 0 &&
                                     ((long long)tgrid * ds.nlights >= YRT_SHADOW_PERSIST_MIN_ITEMS ||
                                      ds.lists_mode == 1 || stage);
+        // ... which shades its items too (k_shadow_shade_persist: no occlusion bytes, no k_shade
+        // launch) where an item is whole pixels and a lane's lights fit its mask
+        const bool shadow_shade = YRT_SHADOW_SHADE_KERNEL && shadow_persist && !stage &&
+                                  nlevels == 1 && !passes && 64 % spp == 0 && ds.nlights <= 32;
         // ... and walk the bundles' candidate lists (k_bundle_lists) instead of the tree
         const bool bundles_possible = YRT_SHADOW_BUNDLES && !stage && shadow_persist &&
                                       bundle_lights(ds.nlights) > 0 && ds.view.nwtop >= YRT_BUNDLE_MIN_TOP;
@@ -2897,7 +3151,13 @@ hipError_t run(device_scene& ds, const dev_render_args& A, float4* out, unsigned
                         hipLaunchKernelGGL((k_shadow_persist<L>), dim3(nb), dim3(SP_BLOCK), 0, stream, ds.view,
                                            nsamp, tgrid, B, counters, cam4);
                         ds.last_lds_staging |= 2;
-                    } else
+                    }
+#if (YRT_SHADOW_SHADE_KERNEL)
+                    else if (shadow_shade)
+                        hipLaunchKernelGGL(k_shadow_shade_persist, dim3(nb), dim3(SP_BLOCK), 0, stream, ds.view, A,
+                                           nsamp, tgrid, B, counters, C, out);
+#endif
+                    else
                         hipLaunchKernelGGL((k_shadow_persist<0>), dim3(nb), dim3(SP_BLOCK), 0, stream, ds.view,
                                            nsamp, tgrid, B, counters, cam4);
                 } else if (!COUNT && PACKET && ds.wide_ok)
@@ -2908,6 +3168,8 @@ hipError_t run(device_scene& ds, const dev_render_args& A, float4* out, unsigned
                                        stream, ds.view, level, nsamp, B, counters, cam4);
                 T.end(t, stream);
             }
+            // (k_shadow_shade_persist has shaded the chunk and written its pixels)
+            if (level == 0 && shadow_shade) continue;
             t = T.begin(phase_shade, stream);
             const bool occ4 = ds.nlights <= 4;
 #define YRT_SHADE_LAUNCH(FU, SBV, GRID)                                                                          \
