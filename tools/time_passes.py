@@ -7,8 +7,9 @@ Renders the frame into device planes on one stream and reports, as medians over 
 calls after `--warmup` calls, the per-phase GPU ms of yrt_last_timings (timing = 1) and their
 sum for yrt_render, for yrt_render_passes with all five passes and the beauty, and for
 yrt_render_passes with `--passes` alone and no beauty; the passes' sums over yrt_render's; the
-sha256 of yrt_render's frame (profiles/frame_digests.json) and whether the passes' beauty has
-the same bits. --lib times another build of the library (tools/build_rev.py); one that has no
+sha256 of yrt_render's frame (profiles/frame_digests.json), of the six planes of the call with
+all passes (passes_sha256: the five passes and the beauty) and whether that beauty has the
+frame's bits. --lib times another build of the library (tools/build_rev.py); one that has no
 yrt_render_passes gives the yrt_render part alone. Prints one JSON line; --out also writes it
 to a file. Needs the GPU: without one it fails.
 """
@@ -116,7 +117,8 @@ def main():
         beauty = torch.zeros_like(frame)
         res["passes_all"] = measure(passes_call(list(N.PASSES), beauty))
         res["passes_all"]["over_render"] = round(res["passes_all"]["ms"] / res["render"]["ms"], 4)
-        res["passes_beauty_same_bits"] = digest(beauty) == res["frame_sha256"]
+        res["passes_sha256"] = dict({n: digest(planes[n]) for n in N.PASSES}, beauty=digest(beauty))
+        res["passes_beauty_same_bits"] = res["passes_sha256"]["beauty"] == res["frame_sha256"]
         names = a.passes.split(",")
         res["passes_partial"] = dict(measure(passes_call(names, None)), passes=names)
         res["passes_partial"]["over_render"] = round(res["passes_partial"]["ms"] / res["render"]["ms"], 4)

@@ -33,6 +33,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <stdexcept>
+#include <type_traits>
 
 #include "packet_trace.h"
 #include "trace_common.h"
@@ -1099,6 +1100,8 @@ __global__ __launch_bounds__(shadow_block<PACKET>(), YRT_SHADOW_WAVES) void k_sh
 // -- with the view point of the zero-light-term cull taken per sample from the ray's own origin
 // (ray_origin) instead of the camera's. A kernel of its own, not a flag of k_shadow: the
 // render's kernels keep the code they have. Every lane of a partial block reaches the walk.
+// (Not a device function shared with k_shadow, neither for the sample's body nor for the whole
+// kernel body: either changes the instructions of every k_shadow, a timed kernel of the frame.)
 template <bool PACKET, typename SE, bool WIDE>
 __global__ __launch_bounds__(shadow_block<PACKET>(), YRT_SHADOW_WAVES) void k_rays_shadow(dev_scene_view S, int nsamp,
                                                                                           wf_buffers B,
@@ -2088,20 +2091,31 @@ __global__ __launch_bounds__(SP_BLOCK, YRT_SHADOW_WAVES) void k_shadow_persist(d
 #endif
 // shade() for one sample that hit (info >= 0), raytrace.cpp:99-206: the surface rows, the
 // material, the textures, the lights that are not occluded, the mirror branch. Every kernel
-// that shades calls this one body (k_shade, k_rays_shade and k_shadow_shade_persist's epilogue):
-// the image is bit-exact because they run the same operations in the same order.
+// that shades calls this one body (k_shade, k_rays_shade, k_shade_passes and
+// k_shadow_shade_persist's epilogue): the image, the ray batches and the passes are bit-exact
+// because they run the same operations in the same order.
 // OCC4: the lights' occlusion is the mask occ_bits, else the bytes B.occl.
 // LATE (k_shadow_shade_persist, at the any-hit grid's 64 VGPRs): what only the end needs, la and
 // kr and the reflective flag, is computed or loaded again after the light loop instead of held
 // across it; the same operations on the same values, 7 VGPR spills fewer.
+// TERMS (the shading passes, k_shade_passes): *terms collects the terms the beauty adds up, as
+// they are computed; with the default, an empty type, nothing of it is compiled.
+struct no_terms {};
+struct pass_terms {
+    // c after the light loop, its ld and ls parts, the vector added for the mirror ray where
+    // max_depth cuts it (0 * kr), la. A sample that never gets here keeps +0 in each.
+    vec3f c = {0, 0, 0}, d = {0, 0, 0}, s = {0, 0, 0}, r = {0, 0, 0}, la = {0, 0, 0};
+};
 __device__ __forceinline__ vec3f amb_of(const vec3f& a) { return a; }
 __device__ __forceinline__ vec3f amb_of(const float* a) { return {a[0], a[1], a[2]}; }  // (LATE: read where it is used)
-template <bool COUNT, bool FUSE, bool OCC4, bool LATE = false, class AMB = vec3f>
+template <bool COUNT, bool FUSE, bool OCC4, bool LATE = false, class AMB = vec3f, class TERMS = no_terms>
 __device__ __forceinline__ void shade_hit(const dev_scene_view& S, const wf_buffers& B, int idx, int info,
                                           const float4& s0, const float4& ro4, uint32_t occ_bits, int level,
                                           int max_depth, const AMB& amb, const float* lut, work_counts& wc,
                                           unsigned long long& truncated, vec3f& R, vec3f& p, bool& spawn, vec3f& dr,
-                                          vec3f& rec_d, vec3f& rec_la, int& rec_mat, bool& write_r) {
+                                          vec3f& rec_d, vec3f& rec_la, int& rec_mat, bool& write_r,
+                                          TERMS* terms = nullptr) {
+    constexpr bool SPLIT = !std::is_same<TERMS, no_terms>::value;
     vec3f nrm;
     vec2f uv;
     int mat, kind;
@@ -2171,6 +2185,7 @@ __device__ __forceinline__ void shade_hit(const dev_scene_view& S, const wf_buff
             ls = ls * spec_pow(smax(0.0f, dot(nrm, h)), ns, ls);
         }
         c = c + (ld + ls);
+        if constexpr (SPLIT) terms->d = terms->d + ld, terms->s = terms->s + ls;
     }
     if (LATE) {
         la = amb_of(amb) * kd0;
@@ -2182,6 +2197,7 @@ __device__ __forceinline__ void shade_hit(const dev_scene_view& S, const wf_buff
         reflective = ibits(ld4(ml + 3).w) & mat_reflective;
         if (reflective) kr = xyz(ld4(ml + 2));
     }
+    if constexpr (SPLIT) terms->c = c, terms->la = la;
     if (!reflective) {
         R = c + la;
     } else if (FUSE || level + 1 >= max_depth || level + 1 >= B.nlevels) {
@@ -2189,6 +2205,7 @@ __device__ __forceinline__ void shade_hit(const dev_scene_view& S, const wf_buff
         // depth cap: the reflected contribution counts as a miss (col = 0)
         truncated++;
         vec3f t = {0.0f * kr.x, 0.0f * kr.y, 0.0f * kr.z};
+        if constexpr (SPLIT) terms->r = t;
         R = (c + t) + la;
     } else {
         spawn = true;
@@ -2234,23 +2251,52 @@ __device__ __forceinline__ void sum_pixels(const dev_render_args& A, const chunk
     }
 }
 
+// the table a texture lookup ends in (YRT_SHADE_LDS_SRGB: the block's LDS copy, staged here by
+// its BS threads). A scene without textures never looks the table up: it is not staged.
+// BARRIER: the copy is followed by its barrier here; otherwise by one of the caller's
+using srgb_table = float[YRT_SHADE_LDS_SRGB ? 256 : 1];
+template <int BS, bool BARRIER>
+__device__ __forceinline__ const float* stage_srgb(const dev_scene_view& S, srgb_table& srgb_lds) {
+    if (YRT_SHADE_LDS_SRGB && S.ntextures > 0) {  // uniform over the grid
+        for (int q = (int)threadIdx.x; q < 256; q += BS) srgb_lds[q] = S.srgb[q];
+        if (BARRIER) __syncthreads();
+    }
+    return YRT_SHADE_LDS_SRGB ? srgb_lds : S.srgb;
+}
+
+// ---- shading passes (yrt_render_passes): the beauty split into the terms shade() adds up ----
+// Per camera sample: DIRECT is c after the light loop (raytrace.cpp:121-185), DIFFUSE and
+// SPECULAR the same chain of adds over the same lights with ld or ls alone, REFLECTION the
+// vector added at raytrace.cpp:203 (col * kr; 0 * kr where max_depth cuts the mirror ray, +0
+// on a material that does not reflect), AMBIENT la. A miss adds +0 to every pass. Each plane
+// is the beauty's box filter of its value: the ordered sum over jj/ii divided by float(s*s).
+// The beauty is plane pass_count of the same kernels. The unfused k_shade_passes is
+// shade_samples, the body of k_shade, with PASSES set: the same statements shade (shade_hit),
+// fold and compact, and what the passes add stands under `if constexpr (PASSES)`, of which the
+// beauty's kernels compile nothing. The fused k_shade_passes keeps a body of its own (there).
+constexpr int pass_planes = pass_count + 1;  // the five passes and the beauty
+struct pass_buffers {
+    unsigned mask;            // bit k: plane k is wanted (bit pass_count: the beauty)
+    float4* out[pass_planes];  // the caller's planes (window layout, out_stride); null when not wanted
+    f4* smp[pass_count];      // per-sample values of a wanted pass (unfused and mirror shapes only)
+};
+
+// The body of every kernel that shades after the queries: k_shade, k_rays_shade and
+// k_shade_passes keep their own names, arguments and launch bounds.
 // RAYS (a ray batch, unfused, k_rays_shade): level 0's view point -- shading and the mirror-ray
 // spawn -- is the sample's own ray origin (ray_origin), and B.rad is the caller's output, one
 // RGBA per ray
-// (the kernels' body: k_shade and k_rays_shade keep their own names and launch bounds)
-template <bool COUNT, bool FUSE, int SB, bool OCC4, bool RAYS>
+// PASSES (the unfused k_shade_passes; P its planes): the terms of each camera sample go to
+// P.smp, the reflection term of a sample with a mirror ray where the fold reaches it
+template <bool COUNT, bool FUSE, int SB, bool OCC4, bool RAYS, bool PASSES = false>
 __device__ __forceinline__ void shade_samples(dev_scene_view S, dev_render_args A, int level, int nsamp_level0,
                                               int max_depth, wf_buffers B, unsigned long long* counters, chunk_args C,
-                                              float4* __restrict__ out) {
+                                              float4* __restrict__ out, const pass_buffers* P = nullptr) {
+    static_assert(!(PASSES && FUSE), "the fused passes kernel has its own body");
     __shared__ float4 fused_rad[FUSE ? SB : 1];
     __shared__ int cmp_count[SB / 64], cmp_base[SB / 64];
-    __shared__ float srgb_lds[YRT_SHADE_LDS_SRGB ? 256 : 1];
-    // (a scene without textures never looks the table up: it is not staged)
-    const float* lut = YRT_SHADE_LDS_SRGB ? srgb_lds : S.srgb;
-    if (YRT_SHADE_LDS_SRGB && S.ntextures > 0) {  // uniform over the grid
-        for (int q = (int)threadIdx.x; q < 256; q += SB) srgb_lds[q] = S.srgb[q];
-        __syncthreads();
-    }
+    __shared__ srgb_table srgb_lds;
+    const float* lut = stage_srgb<SB, true>(S, srgb_lds);
     work_counts wc;
     unsigned long long truncated = 0;
     const vec3f amb = {A.amb[0], A.amb[1], A.amb[2]};
@@ -2300,9 +2346,26 @@ __device__ __forceinline__ void shade_samples(dev_scene_view S, dev_render_args 
                 pd = ld4(B.rec0(level - 1) + parent), pla = ld4(B.rec1(level - 1) + parent);
                 pkr = ld4(S.mats + 4 * ibits(pd.w) + 2);
             }
+            // this sample's pass values (level 0): a miss keeps +0 in each. (Without PASSES an
+            // empty object and a null pointer: with its address k_shade came out differently)
+            typename std::conditional<PASSES, pass_terms, no_terms>::type T;
             if (info >= 0) {
                 shade_hit<COUNT, FUSE, OCC4>(S, B, idx, info, s0, ro4, occ_bits, level, max_depth, amb, lut, wc,
-                                             truncated, R, p, spawn, dr, rec_d, rec_la, rec_mat, write_r);
+                                             truncated, R, p, spawn, dr, rec_d, rec_la, rec_mat, write_r,
+                                             PASSES ? &T : nullptr);
+            }
+            if constexpr (PASSES) {
+                if (level == 0 && info != -2) {
+                    // level 0's values per sample; a sample that spawns a mirror ray gets its
+                    // reflection value where the fold reaches it
+                    const unsigned m = P->mask;
+                    if (m >> pass_direct & 1) gstore(P->smp[pass_direct], idx, T.c.x, T.c.y, T.c.z, 0.0f);
+                    if (m >> pass_diffuse & 1) gstore(P->smp[pass_diffuse], idx, T.d.x, T.d.y, T.d.z, 0.0f);
+                    if (m >> pass_specular & 1) gstore(P->smp[pass_specular], idx, T.s.x, T.s.y, T.s.z, 0.0f);
+                    if (m >> pass_ambient & 1) gstore(P->smp[pass_ambient], idx, T.la.x, T.la.y, T.la.z, 0.0f);
+                    if ((m >> pass_reflection & 1) && !spawn)
+                        gstore(P->smp[pass_reflection], idx, T.r.x, T.r.y, T.r.z, 0.0f);
+                }
             }
             if (FUSE) {
                 fused_rad[threadIdx.x] = make_float4(R.x, R.y, R.z, 1.0f);
@@ -2320,7 +2383,12 @@ __device__ __forceinline__ void shade_samples(dev_scene_view S, dev_render_args 
                     const float4 la = pre ? pla : ld4(B.rec1(lev - 1) + parent);
                     const float4 kr = pre ? pkr : ld4(S.mats + 4 * ibits(d.w) + 2);  // the parent's material kr
                     vec3f cc = {d.x, d.y, d.z};
-                    cc = cc + vec3f{col.x * kr.x, col.y * kr.y, col.z * kr.z};
+                    const vec3f t = {col.x * kr.x, col.y * kr.y, col.z * kr.z};
+                    if constexpr (PASSES) {  // the last step, into the camera sample, adds its reflection value
+                        if (lev == 1 && (P->mask >> pass_reflection & 1))
+                            gstore(P->smp[pass_reflection], parent, t.x, t.y, t.z, 0.0f);
+                    }
+                    cc = cc + t;
                     cc = cc + xyz(la);
                     col = cc, node = parent, lev--;
                 }
@@ -2387,6 +2455,184 @@ __global__ __launch_bounds__(WF_BLOCK, YRT_SHADE_LEVEL_WAVES) void k_rays_shade(
     shade_samples<false, false, WF_BLOCK, OCC4, true>(S, A, level, nsamp_level0, max_depth, B, counters, C, nullptr);
 }
 
+// the shading passes (yrt_render_passes). Unfused (mirror levels, or pixels that are not whole
+// in a block): shade_samples. Fused: a body of its own, with shade_hit's arithmetic written out
+// and the two more accumulators (d, s) beside c. Through shade_hit's TERMS the fused kernel was
+// measurably slower, and so was this body with small changes of form: its own sRGB
+// staging (not stage_srgb) and the loop over its one segment are what keeps the compiler's
+// output. A change to shade_hit is to be made here too (tests/test_gpu_passes*.py compare its
+// beauty with k_shade's bit for bit).
+// Fused: 70-72 VGPRs and no scratch; at k_shade's 7 waves d and s put 32 bytes per lane into
+// scratch
+constexpr int shade_pass_waves = 6;
+template <bool FUSE, int SB = WF_BLOCK, bool OCC4 = false>
+__global__ __launch_bounds__(SB, FUSE ? shade_pass_waves : YRT_SHADE_LEVEL_WAVES) void k_shade_passes(
+    dev_scene_view S, dev_render_args A, int level, int nsamp_level0, int max_depth, wf_buffers B, pass_buffers P,
+    unsigned long long* counters, chunk_args C) {
+    if constexpr (!FUSE) {
+        shade_samples<false, false, SB, OCC4, false, true>(S, A, level, nsamp_level0, max_depth, B, counters, C, nullptr,
+                                                           &P);
+        return;
+    }
+    // the per-sample values of a block's whole pixels, one row of SB floats per (plane,
+    // component): 12 bytes per sample and plane, 18 KiB for the six planes, so eight blocks
+    // still fit a CU's 160 KiB and the LDS does not bound the kernel's 6 waves per SIMD. The
+    // rows are one float apart in the banks, so the 18 chains of a pixel read 18 banks
+    constexpr int ROW = SB + 1;
+    __shared__ float fused[FUSE ? pass_planes * 3 * ROW : 1];
+    __shared__ float srgb_lds[YRT_SHADE_LDS_SRGB ? 256 : 1];
+    const float* lut = YRT_SHADE_LDS_SRGB ? srgb_lds : S.srgb;
+    if (YRT_SHADE_LDS_SRGB && S.ntextures > 0) {  // uniform over the grid
+        for (int q = (int)threadIdx.x; q < 256; q += SB) srgb_lds[q] = S.srgb[q];
+        __syncthreads();
+    }
+    work_counts wc;
+    unsigned long long truncated = 0;
+    const vec3f amb = {A.amb[0], A.amb[1], A.amb[2]};
+    const vec3f cam_o = {A.cam.ox, A.cam.oy, A.cam.oz};
+    const int stride = gridDim.x * SB;
+    for (int g = 0; g < 1; g++) {  // (shade_samples' loop over segments: level 0 has one)
+    const int n = nsamp_level0;
+    const int nround = (n + stride - 1) / stride;
+    for (int round = 0; round < nround; round++) {
+        const int j = round * stride + blockIdx.x * SB + threadIdx.x;
+        const int idx = j;
+        vec3f p = {0, 0, 0};
+        // this sample's pass values (level 0): a miss and a lane past the chunk keep +0
+        vec3f R = {0, 0, 0}, pc = {0, 0, 0}, pd = {0, 0, 0}, ps = {0, 0, 0}, pr = {0, 0, 0}, pla = {0, 0, 0};
+        if (j < n) {
+            float4 s0 = ld4s(B.surf0 + idx);
+            uint32_t occ_bits = 0;
+            if constexpr (OCC4) {
+#pragma unroll
+                for (int q = 0; q < 4; q++) {
+                    const int lq = q < S.nlights ? q : 0;  // an unconditional load, masked after
+                    const uint32_t ob = ldb(B.occl + (size_t)lq * B.capacity + idx);
+                    occ_bits |= (q < S.nlights && ob != 0u) ? 1u << q : 0u;
+                }
+            }
+            const int info = sample_state(s0);
+            const float4 ro4 = make_float4(cam_o.x, cam_o.y, cam_o.z, 0.0f);
+            if (info >= 0) {
+                vec3f nrm;
+                vec2f uv;
+                int mat, kind;
+                if (YRT_HIT16) {
+                    const surface sf = hit16_surface(S, s0);
+                    p = sf.p, nrm = sf.n, uv = sf.uv, mat = sf.mat, kind = sf.kind;
+                } else {
+                    const float4 s1 = ld4s(B.surf1 + idx);
+                    p = xyz(s0), nrm = xyz(s1), uv = {s1.w, (!YRT_SKIP_UNUSED_V || B.need_v) ? lds1(B.surfv + idx) : 0.0f};
+                    mat = info_mat(info), kind = info & 3;
+                }
+                const vec3f ro = xyz(ro4);
+                const float4 m0 = ld4(S.mats + 4 * mat), m1 = ld4(S.mats + 4 * mat + 1);
+                const float4 m2 = ld4(S.mats + 4 * mat + 2), m3 = ld4(S.mats + 4 * mat + 3);
+                const vec3f kd0 = xyz(m0), ks0 = xyz(m1), kr = xyz(m2);
+                const float ns = m0.w;
+                const int kd_txt = ibits(m1.w), ks_txt = ibits(m2.w);
+                const bool reflective = ibits(m3.w) & mat_reflective;
+                vec3f la = amb * kd0;
+                vec3f tkd = {1, 1, 1}, tks = {1, 1, 1};
+                if (kd_txt >= 0) {
+                    tkd = eval_texture<false>(S, kd_txt, uv, wc, lut);
+                    la = la * tkd;
+                }
+                if (ks_txt >= 0) tks = eval_texture<false>(S, ks_txt, uv, wc, lut);
+                vec3f c = {0.0f, 0.0f, 0.0f}, cd = {0.0f, 0.0f, 0.0f}, cs = {0.0f, 0.0f, 0.0f};
+                vec3f v;
+                float vlen;
+                normalize_len(ro - p, v, vlen);
+                for (int li = 0; li < S.nlights; li++) {
+                    if (OCC4 ? ((occ_bits >> li) & 1u) != 0u : ldb(B.occl + (size_t)li * B.capacity + idx) != 0) continue;
+                    const f4* lr = S.lights + 6 * li;
+                    float4 lrec[6];
+                    ld_scalar<6>(lr, lrec);
+                    frame3f lf = {xyz(lrec[0]), xyz(lrec[1]), xyz(lrec[2]), xyz(lrec[3])};
+                    vec3f lp0 = xyz(lrec[4]), ke = xyz(lrec[5]);
+                    vec3f tp = transform_point(lf, lp0 - p);
+                    vec3f l, h;
+                    float r, hlen;
+                    normalize_len(tp, l, r);
+                    normalize_len(v + l, h, hlen);
+                    vec3f kd = kd0, ks = ks0;
+                    if (kd_txt >= 0) kd = kd * tkd;
+                    if (ks_txt >= 0) ks = ks * tks;
+                    const vec3f ker = div3(ke, r * r);
+                    vec3f ld = kd * ker;
+                    vec3f ls = ks * ker;
+                    if (kind == kind_lines) {
+                        float prodnl = dot(nrm, l);
+                        float prodnh = dot(nrm, h);
+                        if (prodnl < 0.0f) prodnl *= -1;
+                        if (prodnh < 0.0f) prodnh *= -1;
+                        float sinnl = __builtin_sqrtf(1.0f - prodnl);
+                        float sinnh = __builtin_sqrtf(1.0f - prodnh);
+                        ld = ld * sinnl;
+                        ls = ls * spec_pow(sinnh, ns, ls);
+                    } else {
+                        ld = ld * smax(0.0f, dot(nrm, l));
+                        ls = ls * spec_pow(smax(0.0f, dot(nrm, h)), ns, ls);
+                    }
+                    c = c + (ld + ls);
+                    cd = cd + ld;
+                    cs = cs + ls;
+                }
+                pc = c, pd = cd, ps = cs, pla = la;
+                if (!reflective) {
+                    R = c + la;
+                } else {
+                    // depth cap: the reflected contribution counts as a miss (col = 0)
+                    truncated++;
+                    vec3f t = {0.0f * kr.x, 0.0f * kr.y, 0.0f * kr.z};
+                    pr = t;
+                    R = (c + t) + la;
+                }
+            }
+        }
+        if constexpr (FUSE) {
+            // (one round per block: the rows are written once)
+            auto put = [&](int k, const vec3f& val) {
+                if (!(P.mask >> k & 1)) return;  // (uniform)
+                fused[(k * 3 + 0) * ROW + threadIdx.x] = val.x;
+                fused[(k * 3 + 1) * ROW + threadIdx.x] = val.y;
+                fused[(k * 3 + 2) * ROW + threadIdx.x] = val.z;
+            };
+            put(pass_direct, pc), put(pass_diffuse, pd), put(pass_specular, ps);
+            put(pass_reflection, pr), put(pass_ambient, pla), put(pass_count, R);
+            continue;  // one level: no mirror rays
+        }
+    }
+    }
+    if (FUSE) {
+        // raytrace.cpp:232-249 per plane: one lane per (pixel, plane, colour component), each
+        // lane's sum the reference's ordered chain of adds for that component
+        __syncthreads();
+        const int ppb = SB / C.spp;
+        for (int t = (int)threadIdx.x; t < 3 * pass_planes * ppb; t += SB) {
+            const int px = t / (3 * pass_planes), r = t - 3 * pass_planes * px;
+            const int k = r / 3, comp = r - 3 * k;
+            if (!(P.mask >> k & 1)) continue;
+            const int pl = (int)(blockIdx.x * SB / C.spp) + px;
+            int lx, ly, i, j;
+            const bool valid = pl < C.npix && pixel_of(A, C.tiles_x, C.pix0 + pl, lx, ly, i, j);
+            if (pl < C.npix && lx < A.tile_w && ly < A.tile_h) {
+                float v = 0.0f;
+                if (valid) {
+                    const float* row = fused + (k * 3 + comp) * ROW + px * C.spp;
+                    float acc = 0.0f;
+                    for (int q = 0; q < C.spp; q++) acc = acc + row[q];
+                    v = acc / float(C.spp);
+                }
+                float* o = reinterpret_cast<float*>(P.out[k] + (size_t)ly * A.out_stride + lx);
+                o[comp] = v;
+                if (comp == 0) o[3] = valid ? 1.0f : 0.0f;
+            }
+        }
+    }
+    flush(counters, cnt_depth_truncated, truncated);
+}
+
 // ---- level 0's shadow rays and shading in one persistent grid ----
 #if !defined(YRT_SHADOW_SHADE_FUSE)  // (its non-default build is the `unfused` library of tools/build_variants.py)
 // one level, 1 / 4 / 16 / 64 spp, at most 32 lights: an item of the any-hit grid (a 64-sample
@@ -2419,7 +2665,7 @@ __global__ __launch_bounds__(SP_BLOCK, YRT_SHADOW_WAVES) void k_shadow_shade_per
     constexpr unsigned RUN = YRT_SHADOW_ITEM_RUN;
     __shared__ float4 wave_rad[WPB][64];
     __shared__ unsigned wave_truncated[WPB];  // (in LDS: a register would be live across the walks)
-    __shared__ float srgb_lds[YRT_SHADE_LDS_SRGB ? 256 : 1];
+    __shared__ srgb_table srgb_lds;
     // the epilogue reads the frame's and the chunk's arguments from an LDS copy, per item: as
     // scalars they and what the compiler derives from them ahead of the loop (the reciprocals
     // of the pixel enumeration's divisors, float(spp)) would be held across the walks
@@ -2427,9 +2673,7 @@ __global__ __launch_bounds__(SP_BLOCK, YRT_SHADOW_WAVES) void k_shadow_shade_per
         dev_render_args A;
         chunk_args C;
     } args;
-    const float* lut = YRT_SHADE_LDS_SRGB ? srgb_lds : S.srgb;
-    if (YRT_SHADE_LDS_SRGB && S.ntextures > 0)  // uniform over the grid
-        for (int q = (int)threadIdx.x; q < 256; q += SP_BLOCK) srgb_lds[q] = S.srgb[q];
+    const float* lut = stage_srgb<SP_BLOCK, false>(S, srgb_lds);  // (its barrier: the one below)
     if (threadIdx.x == 0) args.A = A, args.C = C;
     __syncthreads();
     // (the view point as three scalars of their own, not as part of the four-dword kernel-argument
@@ -2521,295 +2765,19 @@ __global__ __launch_bounds__(SP_BLOCK, YRT_SHADOW_WAVES) void k_shadow_shade_per
 // wave stages them through LDS AQ samples of every pixel at a time with loads in which
 // neighbouring lanes read neighbouring samples (a pixel's AQ samples are one contiguous
 // run), then each lane adds its own pixel's samples in the reference's order.
+// One plane: the chunk's per-sample values samples() summed into the window out() (the body of
+// k_accumulate and, per plane, of k_accumulate_passes). The two pointers come as callables,
+// read where they are used, and A and C by value as the kernels take them: so both kernels
+// compile to the instructions they had with a body each.
 constexpr int AQ = 8;
-__global__ __launch_bounds__(WF_BLOCK) void k_accumulate(dev_render_args A, chunk_args C, wf_buffers B,
-                                                         float4* __restrict__ out) {
+template <class SMP, class OUT>
+__device__ __forceinline__ void accumulate_plane(dev_render_args A, chunk_args C, SMP&& samples, OUT&& out) {
     __shared__ float4 stage[WF_BLOCK / 64][64 * (AQ + 1)];  // rows padded against bank conflicts
     const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int pl0 = blockIdx.x * WF_BLOCK + w * 64;
     const int np = max(0, min(64, C.npix - pl0));  // pixels of this wave
     float4* S = stage[w];
-    const f4* base = B.rad + (size_t)pl0 * C.spp;
-    vec4f acc = {0, 0, 0, 0};
-    for (int q0 = 0; q0 < C.spp; q0 += AQ) {  // the same trip count in every wave of the block
-        const int qn = min(AQ, C.spp - q0);
-        for (int e = lane; e < np * qn; e += 64) {
-            const int px = e / qn, q = e % qn;
-            S[px * (AQ + 1) + q] = ld4(base + (size_t)px * C.spp + q0 + q);
-        }
-        __syncthreads();
-        if (lane < np)
-            for (int q = 0; q < qn; q++) {
-                const float4 c = S[lane * (AQ + 1) + q];
-                acc = {acc.x + c.x, acc.y + c.y, acc.z + c.z, acc.w + 1.0f};
-            }
-        __syncthreads();
-    }
-    if (lane >= np) return;
-    const int pl = pl0 + lane;
-    int lx, ly, i, j;
-    const bool valid = pixel_of(A, C.tiles_x, C.pix0 + pl, lx, ly, i, j);
-    if (lx >= A.tile_w || ly >= A.tile_h) return;
-    const float d = float(C.spp);
-    out[(size_t)ly * A.out_stride + lx] =
-        valid ? make_float4(acc.x / d, acc.y / d, acc.z / d, 1.0f) : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-}
-
-// ---- shading passes (yrt_render_passes): the beauty split into the terms shade() adds up ----
-// Per camera sample: DIRECT is c after the light loop (raytrace.cpp:121-185), DIFFUSE and
-// SPECULAR the same chain of adds over the same lights with ld or ls alone, REFLECTION the
-// vector added at raytrace.cpp:203 (col * kr; 0 * kr where max_depth cuts the mirror ray, +0
-// on a material that does not reflect), AMBIENT la. A miss adds +0 to every pass. Each plane
-// is the beauty's box filter of its value: the ordered sum over jj/ii divided by float(s*s).
-// The beauty is plane pass_count of the same kernels, computed exactly as k_shade and
-// k_accumulate compute it. The kernels below are k_shade's and k_accumulate's bodies again,
-// not a shared function: the beauty path keeps the code it has.
-constexpr int pass_planes = pass_count + 1;  // the five passes and the beauty
-struct pass_buffers {
-    unsigned mask;            // bit k: plane k is wanted (bit pass_count: the beauty)
-    float4* out[pass_planes];  // the caller's planes (window layout, out_stride); null when not wanted
-    f4* smp[pass_count];      // per-sample values of a wanted pass (unfused and mirror shapes only)
-};
-
-// fused k_shade_passes: 70-72 VGPRs and no scratch; at k_shade's 7 waves the two more
-// accumulators (d, s) put 32 bytes per lane into scratch
-constexpr int shade_pass_waves = 6;
-template <bool FUSE, int SB = WF_BLOCK, bool OCC4 = false>
-__global__ __launch_bounds__(SB, FUSE ? shade_pass_waves : YRT_SHADE_LEVEL_WAVES) void k_shade_passes(
-    dev_scene_view S, dev_render_args A, int level, int nsamp_level0, int max_depth, wf_buffers B, pass_buffers P,
-    unsigned long long* counters, chunk_args C) {
-    // the per-sample values of a block's whole pixels, one row of SB floats per (plane,
-    // component): 12 bytes per sample and plane, 18 KiB for the six planes, so eight blocks
-    // still fit a CU's 160 KiB and the LDS does not bound the kernel's 6 waves per SIMD. The
-    // rows are one float apart in the banks, so the 18 chains of a pixel read 18 banks
-    constexpr int ROW = SB + 1;
-    __shared__ float fused[FUSE ? pass_planes * 3 * ROW : 1];
-    __shared__ int cmp_count[SB / 64], cmp_base[SB / 64];
-    __shared__ float srgb_lds[YRT_SHADE_LDS_SRGB ? 256 : 1];
-    const float* lut = YRT_SHADE_LDS_SRGB ? srgb_lds : S.srgb;
-    if (YRT_SHADE_LDS_SRGB && S.ntextures > 0) {  // uniform over the grid
-        for (int q = (int)threadIdx.x; q < 256; q += SB) srgb_lds[q] = S.srgb[q];
-        __syncthreads();
-    }
-    work_counts wc;
-    unsigned long long truncated = 0;
-    const vec3f amb = {A.amb[0], A.amb[1], A.amb[2]};
-    const vec3f cam_o = {A.cam.ox, A.cam.oy, A.cam.oz};
-    const int stride = gridDim.x * SB;
-    const int gout = (int)(blockIdx.x % (unsigned)level_segments);
-    const int nseg = FUSE ? 1 : level ? level_segments : 1;
-    for (int g = 0; g < nseg; g++) {
-    const int n = (!FUSE && level) ? *seg_counter(B.count, level, g) : nsamp_level0;
-    const int nround = (n + stride - 1) / stride;
-    for (int round = 0; round < nround; round++) {
-        const int j = round * stride + blockIdx.x * SB + threadIdx.x;
-        const int idx = FUSE ? j : g * B.seg + j;
-        bool spawn = false;
-        vec3f p = {0, 0, 0}, dr = {0, 0, 0}, rec_d = {0, 0, 0}, rec_la = {0, 0, 0};
-        int rec_mat = 0;
-        // this sample's pass values (level 0): a miss and a lane past the chunk keep +0
-        vec3f R = {0, 0, 0}, pc = {0, 0, 0}, pd = {0, 0, 0}, ps = {0, 0, 0}, pr = {0, 0, 0}, pla = {0, 0, 0};
-        if (j < n) {
-            float4 s0 = ld4s(B.surf0 + idx);
-            uint32_t occ_bits = 0;
-            if constexpr (OCC4) {
-#pragma unroll
-                for (int q = 0; q < 4; q++) {
-                    const int lq = q < S.nlights ? q : 0;  // an unconditional load, masked after
-                    const uint32_t ob = ldb(B.occl + (size_t)lq * B.capacity + idx);
-                    occ_bits |= (q < S.nlights && ob != 0u) ? 1u << q : 0u;
-                }
-            }
-            const int info = sample_state(s0);
-            bool write_r = info != -2;
-            const float4 ro4 = (!FUSE && level) ? ld4(B.ray_o(level) + idx) : make_float4(cam_o.x, cam_o.y, cam_o.z, 0.0f);
-            if (info >= 0) {
-                vec3f nrm;
-                vec2f uv;
-                int mat, kind;
-                if (YRT_HIT16) {
-                    const surface sf = hit16_surface(S, s0);
-                    p = sf.p, nrm = sf.n, uv = sf.uv, mat = sf.mat, kind = sf.kind;
-                } else {
-                    const float4 s1 = ld4s(B.surf1 + idx);
-                    p = xyz(s0), nrm = xyz(s1), uv = {s1.w, (!YRT_SKIP_UNUSED_V || B.need_v) ? lds1(B.surfv + idx) : 0.0f};
-                    mat = info_mat(info), kind = info & 3;
-                }
-                const vec3f ro = xyz(ro4);
-                const float4 m0 = ld4(S.mats + 4 * mat), m1 = ld4(S.mats + 4 * mat + 1);
-                const float4 m2 = ld4(S.mats + 4 * mat + 2), m3 = ld4(S.mats + 4 * mat + 3);
-                const vec3f kd0 = xyz(m0), ks0 = xyz(m1), kr = xyz(m2);
-                const float ns = m0.w;
-                const int kd_txt = ibits(m1.w), ks_txt = ibits(m2.w);
-                const bool reflective = ibits(m3.w) & mat_reflective;
-                vec3f la = amb * kd0;
-                vec3f tkd = {1, 1, 1}, tks = {1, 1, 1};
-                if (kd_txt >= 0) {
-                    tkd = eval_texture<false>(S, kd_txt, uv, wc, lut);
-                    la = la * tkd;
-                }
-                if (ks_txt >= 0) tks = eval_texture<false>(S, ks_txt, uv, wc, lut);
-                vec3f c = {0.0f, 0.0f, 0.0f}, cd = {0.0f, 0.0f, 0.0f}, cs = {0.0f, 0.0f, 0.0f};
-                vec3f v;
-                float vlen;
-                normalize_len(ro - p, v, vlen);
-                for (int li = 0; li < S.nlights; li++) {
-                    if (OCC4 ? ((occ_bits >> li) & 1u) != 0u : ldb(B.occl + (size_t)li * B.capacity + idx) != 0) continue;
-                    const f4* lr = S.lights + 6 * li;
-                    float4 lrec[6];
-                    ld_scalar<6>(lr, lrec);
-                    frame3f lf = {xyz(lrec[0]), xyz(lrec[1]), xyz(lrec[2]), xyz(lrec[3])};
-                    vec3f lp0 = xyz(lrec[4]), ke = xyz(lrec[5]);
-                    vec3f tp = transform_point(lf, lp0 - p);
-                    vec3f l, h;
-                    float r, hlen;
-                    normalize_len(tp, l, r);
-                    normalize_len(v + l, h, hlen);
-                    vec3f kd = kd0, ks = ks0;
-                    if (kd_txt >= 0) kd = kd * tkd;
-                    if (ks_txt >= 0) ks = ks * tks;
-                    const vec3f ker = div3(ke, r * r);
-                    vec3f ld = kd * ker;
-                    vec3f ls = ks * ker;
-                    if (kind == kind_lines) {
-                        float prodnl = dot(nrm, l);
-                        float prodnh = dot(nrm, h);
-                        if (prodnl < 0.0f) prodnl *= -1;
-                        if (prodnh < 0.0f) prodnh *= -1;
-                        float sinnl = __builtin_sqrtf(1.0f - prodnl);
-                        float sinnh = __builtin_sqrtf(1.0f - prodnh);
-                        ld = ld * sinnl;
-                        ls = ls * spec_pow(sinnh, ns, ls);
-                    } else {
-                        ld = ld * smax(0.0f, dot(nrm, l));
-                        ls = ls * spec_pow(smax(0.0f, dot(nrm, h)), ns, ls);
-                    }
-                    c = c + (ld + ls);
-                    cd = cd + ld;
-                    cs = cs + ls;
-                }
-                pc = c, pd = cd, ps = cs, pla = la;
-                if (!reflective) {
-                    R = c + la;
-                } else if (FUSE || level + 1 >= max_depth || level + 1 >= B.nlevels) {
-                    // depth cap: the reflected contribution counts as a miss (col = 0)
-                    truncated++;
-                    vec3f t = {0.0f * kr.x, 0.0f * kr.y, 0.0f * kr.z};
-                    pr = t;
-                    R = (c + t) + la;
-                } else {
-                    spawn = true;
-                    dr = (nrm * 2.0f * dot(nrm, v)) - v;
-                    rec_d = c;
-                    rec_la = la;
-                    rec_mat = mat;
-                    write_r = false;
-                }
-            }
-            if (!FUSE && level == 0 && info != -2) {
-                // level 0's values per sample; a sample that spawns a mirror ray gets its
-                // reflection value where the fold reaches it
-                if (P.mask >> pass_direct & 1) gstore(P.smp[pass_direct], idx, pc.x, pc.y, pc.z, 0.0f);
-                if (P.mask >> pass_diffuse & 1) gstore(P.smp[pass_diffuse], idx, pd.x, pd.y, pd.z, 0.0f);
-                if (P.mask >> pass_specular & 1) gstore(P.smp[pass_specular], idx, ps.x, ps.y, ps.z, 0.0f);
-                if (P.mask >> pass_ambient & 1) gstore(P.smp[pass_ambient], idx, pla.x, pla.y, pla.z, 0.0f);
-                if ((P.mask >> pass_reflection & 1) && !spawn) gstore(P.smp[pass_reflection], idx, pr.x, pr.y, pr.z, 0.0f);
-            }
-            if (!FUSE && write_r) {
-                // the fold of k_shade (R_k-1 = (D + R_k * kr) + la); its last step, into the
-                // camera sample, adds that sample's reflection value
-                vec3f col = R;
-                int lev = level, node = idx;
-                while (lev > 0) {
-                    const int parent = ibits(B.ray_o(lev)[node].w);
-                    const float4 d = ld4(B.rec0(lev - 1) + parent);
-                    const float4 la = ld4(B.rec1(lev - 1) + parent);
-                    const float4 kr = ld4(S.mats + 4 * ibits(d.w) + 2);  // the parent's material kr
-                    vec3f cc = {d.x, d.y, d.z};
-                    const vec3f t = {col.x * kr.x, col.y * kr.y, col.z * kr.z};
-                    if (lev == 1 && (P.mask >> pass_reflection & 1))
-                        gstore(P.smp[pass_reflection], parent, t.x, t.y, t.z, 0.0f);
-                    cc = cc + t;
-                    cc = cc + xyz(la);
-                    col = cc, node = parent, lev--;
-                }
-                B.rad[node] = {col.x, col.y, col.z, 1.0f};
-            }
-        }
-        if constexpr (FUSE) {
-            // (one round per block: the rows are written once)
-            auto put = [&](int k, const vec3f& val) {
-                if (!(P.mask >> k & 1)) return;  // (uniform)
-                fused[(k * 3 + 0) * ROW + threadIdx.x] = val.x;
-                fused[(k * 3 + 1) * ROW + threadIdx.x] = val.y;
-                fused[(k * 3 + 2) * ROW + threadIdx.x] = val.z;
-            };
-            put(pass_direct, pc), put(pass_diffuse, pd), put(pass_specular, ps);
-            put(pass_reflection, pr), put(pass_ambient, pla), put(pass_count, R);
-            continue;  // one level: no mirror rays
-        }
-        const unsigned long long mask = __ballot(spawn);
-        const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
-        if (spawn) {
-            B.rec0(level)[idx] = {rec_d.x, rec_d.y, rec_d.z, __int_as_float(rec_mat)};
-            B.rec1(level)[idx] = {rec_la.x, rec_la.y, rec_la.z, 0};
-        }
-        if (lane == 0) cmp_count[w] = __popcll(mask);
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            int tot = 0;
-            for (int q = 0; q < SB / 64; q++) tot += cmp_count[q];
-            int acc = tot ? atomicAdd(seg_counter(B.count, level + 1, gout), tot) : 0;
-            for (int q = 0; q < SB / 64; q++) cmp_base[q] = acc, acc += cmp_count[q];
-        }
-        __syncthreads();
-        if (spawn) {
-            const int slot = gout * B.seg + cmp_base[w] + __popcll(mask & ((1ull << lane) - 1));
-            B.ray_o(level + 1)[slot] = {p.x, p.y, p.z, __int_as_float(idx)};
-            B.ray_d(level + 1)[slot] = {dr.x, dr.y, dr.z, 0};
-        }
-    }
-    }
-    if (FUSE) {
-        // raytrace.cpp:232-249 per plane: one lane per (pixel, plane, colour component), each
-        // lane's sum the reference's ordered chain of adds for that component
-        __syncthreads();
-        const int ppb = SB / C.spp;
-        for (int t = (int)threadIdx.x; t < 3 * pass_planes * ppb; t += SB) {
-            const int px = t / (3 * pass_planes), r = t - 3 * pass_planes * px;
-            const int k = r / 3, comp = r - 3 * k;
-            if (!(P.mask >> k & 1)) continue;
-            const int pl = (int)(blockIdx.x * SB / C.spp) + px;
-            int lx, ly, i, j;
-            const bool valid = pl < C.npix && pixel_of(A, C.tiles_x, C.pix0 + pl, lx, ly, i, j);
-            if (pl < C.npix && lx < A.tile_w && ly < A.tile_h) {
-                float v = 0.0f;
-                if (valid) {
-                    const float* row = fused + (k * 3 + comp) * ROW + px * C.spp;
-                    float acc = 0.0f;
-                    for (int q = 0; q < C.spp; q++) acc = acc + row[q];
-                    v = acc / float(C.spp);
-                }
-                float* o = reinterpret_cast<float*>(P.out[k] + (size_t)ly * A.out_stride + lx);
-                o[comp] = v;
-                if (comp == 0) o[3] = valid ? 1.0f : 0.0f;
-            }
-        }
-    }
-    flush(counters, cnt_depth_truncated, truncated);
-}
-
-// k_accumulate per plane: blockIdx.y is the plane, its samples P.smp[k] (the beauty's B.rad)
-__global__ __launch_bounds__(WF_BLOCK) void k_accumulate_passes(dev_render_args A, chunk_args C, wf_buffers B,
-                                                                pass_buffers P) {
-    __shared__ float4 stage[WF_BLOCK / 64][64 * (AQ + 1)];  // rows padded against bank conflicts
-    const int k = (int)blockIdx.y;
-    if (!(P.mask >> k & 1)) return;  // (uniform over the block)
-    const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const int pl0 = blockIdx.x * WF_BLOCK + w * 64;
-    const int np = max(0, min(64, C.npix - pl0));  // pixels of this wave
-    float4* S = stage[w];
-    const f4* base = (k == pass_count ? B.rad : P.smp[k]) + (size_t)pl0 * C.spp;
+    const f4* base = samples() + (size_t)pl0 * C.spp;
     vec3f acc = {0, 0, 0};
     for (int q0 = 0; q0 < C.spp; q0 += AQ) {  // the same trip count in every wave of the block
         const int qn = min(AQ, C.spp - q0);
@@ -2831,8 +2799,21 @@ __global__ __launch_bounds__(WF_BLOCK) void k_accumulate_passes(dev_render_args 
     const bool valid = pixel_of(A, C.tiles_x, C.pix0 + pl, lx, ly, i, j);
     if (lx >= A.tile_w || ly >= A.tile_h) return;
     const float d = float(C.spp);
-    P.out[k][(size_t)ly * A.out_stride + lx] =
+    out()[(size_t)ly * A.out_stride + lx] =
         valid ? make_float4(acc.x / d, acc.y / d, acc.z / d, 1.0f) : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+}
+
+__global__ __launch_bounds__(WF_BLOCK) void k_accumulate(dev_render_args A, chunk_args C, wf_buffers B,
+                                                         float4* __restrict__ out) {
+    accumulate_plane(A, C, [&] { return B.rad; }, [&] { return out; });
+}
+
+// the shading passes' planes: blockIdx.y is the plane, its samples P.smp[k] (the beauty's B.rad)
+__global__ __launch_bounds__(WF_BLOCK) void k_accumulate_passes(dev_render_args A, chunk_args C, wf_buffers B,
+                                                                pass_buffers P) {
+    const int k = (int)blockIdx.y;
+    if (!(P.mask >> k & 1)) return;  // (uniform over the block)
+    accumulate_plane(A, C, [&] { return k == pass_count ? B.rad : P.smp[k]; }, [&] { return P.out[k]; });
 }
 
 size_t align_up(size_t x) { return (x + 255) & ~size_t(255); }
@@ -2916,6 +2897,90 @@ wf_buffers carve(void* base, int cap, int spp, int nlights, int nlevels) {
     return B;
 }
 
+// ---- the host code of run() and run_rays() ----
+
+// a call without a chunk launches no k_chunk_setup: the counters still start at 0, or
+// yrt_last_stats would report the call before this one
+hipError_t clear_counters(unsigned long long* counters, hipStream_t stream) {
+    return counters ? hipMemsetAsync(counters, 0, (size_t)cnt_slots * cnt_count * sizeof(unsigned long long), stream)
+                    : hipSuccess;
+}
+
+// Samples per chunk, bytes_of(target) being the workspace of a chunk of `target` samples: a
+// whole frame at c3/c4, 15 chunks at c5. A reflective scene keeps per-level records for
+// every level (64 B per sample and level). The chunk is halved until the workspace takes at
+// most half of the free HBM (deep mirror recursions run as more, smaller chunks); a depth
+// whose smallest chunk (2^16 samples, or the knob's own target when that starts lower: the
+// halving never raises it) still does not fit is refused.
+template <class F>
+long long chunk_target(const device_scene& ds, const dev_render_args& A, F&& bytes_of) {
+    long long target = 1ll << (ds.reflective ? MIRROR_CHUNK_LOG2 : CHUNK_LOG2);
+    // the free-memory query (a driver round trip) only when the workspace must grow: a
+    // steady frame loop reuses the workspace it already has
+    if (bytes_of(target) > ds.work_bytes) {
+        size_t free_b = 0, total_b = 0;
+        if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) free_b = 0;
+        free_b += ds.work_bytes;  // the current workspace is given back if it is regrown
+        while (target > (1ll << 16) && bytes_of(target) > free_b / 2) target /= 2;
+        if (bytes_of(target) > free_b)
+            throw unsupported_error("max_depth " + std::to_string(A.max_depth) + " needs " +
+                                    std::to_string(bytes_of(target) >> 20) + " MiB of mirror-level records for its " +
+                                    "smallest chunk; " + std::to_string(free_b >> 20) + " MiB of HBM are free");
+    }
+    return target;
+}
+
+// the handle's workspace holds at least `need` bytes
+hipError_t grow_workspace(device_scene& ds, size_t need) {
+    if (need <= ds.work_bytes) return hipSuccess;
+    if (ds.work) (void)hipFree(ds.work);
+    ds.work = nullptr;
+    ds.work_bytes = 0;
+    hipError_t e = hipMalloc(&ds.work, need);
+    if (e == hipSuccess) ds.work_bytes = need;
+    return e;
+}
+
+// The mirror levels' ray counts on the host. The host reads each level's count (written by the
+// previous level's shading) without draining the stream: the copy is queued behind that
+// shading (fetch_level_counts), the level's k_bounce, which takes its count on the device,
+// behind the copy, and only then does the host wait for the copy (level_has_rays).
+hipError_t make_level_counts(device_scene& ds) {
+    if (!ds.level_count_host) {
+        hipError_t e = hipHostMalloc((void**)&ds.level_count_host, sizeof(int) * level_segments * count_stride,
+                                     hipHostMallocDefault);
+        if (e != hipSuccess) return e;
+    }
+    if (!ds.level_count_ev) return hipEventCreateWithFlags(&ds.level_count_ev, hipEventDisableTiming);
+    return hipSuccess;
+}
+hipError_t fetch_level_counts(device_scene& ds, const wf_buffers& B, int level, hipStream_t stream) {
+    hipError_t e = hipMemcpyAsync(ds.level_count_host, B.count + (size_t)level * level_segments * count_stride,
+                                  sizeof(int) * level_segments * count_stride, hipMemcpyDeviceToHost, stream);
+    return e == hipSuccess ? hipEventRecord(ds.level_count_ev, stream) : e;
+}
+hipError_t level_has_rays(device_scene& ds, bool& any) {
+    hipError_t e = hipEventSynchronize(ds.level_count_ev);
+    any = false;
+    for (int g = 0; e == hipSuccess && g < level_segments; g++) any |= ds.level_count_host[g * count_stride] != 0;
+    return e;
+}
+
+// The chunk's setup (k_chunk_setup): the zeroed work queues and mirror-level counters; in a
+// call's first chunk the zeroed work counters; the zeroed list sums where lstats is given; and
+// the nrec camera-relative instance-level records of a render seen from cam4 (0: none).
+void launch_chunk_setup(const device_scene& ds, const wf_buffers& B, int nrec, const float4& cam4,
+                        unsigned long long* lstats, int nlevels, unsigned long long* counters, bool first_chunk,
+                        hipStream_t stream) {
+    const int count_ints = nlevels > 1 ? (int)(count_bytes(nlevels) / sizeof(int)) : 0;
+    const int counter_words = first_chunk && counters ? cnt_slots * cnt_count : 0;
+    const int work = std::max(std::max(nrec, count_ints), std::max(counter_words, 32));
+    const int nb = std::min((work + WF_BLOCK - 1) / WF_BLOCK, 1024);
+    hipLaunchKernelGGL(k_chunk_setup, dim3(nb), dim3(WF_BLOCK), 0, stream, nrec ? ds.view.tpair : nullptr, nrec,
+                       cam4.x, cam4.y, cam4.z, ds.trel, B.queue, lstats, B.count, count_ints, counters,
+                       counter_words);
+}
+
 // passes: yrt_render_passes' planes (P.mask, P.out; out is then P.out[pass_count], the beauty,
 // or null), shaded by k_shade_passes and summed by k_accumulate_passes; null: yrt_render
 template <bool COUNT, bool PACKET, typename SE>
@@ -2928,13 +2993,6 @@ hipError_t run(device_scene& ds, const dev_render_args& A, float4* out, unsigned
     // one level per trace_first call a camera sample may make (A.max_depth; the reference
     // recursion is unbounded, so the caller's depth is kept as given)
     const int nlevels = ds.reflective ? std::max(A.max_depth, 1) : 1;
-    // samples per chunk: a whole frame at c3/c4, 15 chunks at c5. A reflective scene keeps
-    // per-level records for every level (64 B per sample and level). The chunk is halved
-    // until the workspace takes at most half of the free HBM (deep mirror recursions run
-    // as more, smaller chunks); a depth whose smallest chunk (2^16 samples, or the knob's
-    // own target when that starts lower: the halving never raises it) still does not fit is
-    // refused.
-    long long target = 1ll << (ds.reflective ? MIRROR_CHUNK_LOG2 : CHUNK_LOG2);
     auto cap_for = [&](long long tgt) {
         int pix = (int)std::max<long long>(1, std::min<long long>(npix_total, tgt / spp));
         pix = ((pix + TILE * TILE - 1) / (TILE * TILE)) * TILE * TILE;
@@ -2957,30 +3015,11 @@ hipError_t run(device_scene& ds, const dev_render_args& A, float4* out, unsigned
         const int pix = cap_for(tgt);
         return workspace_bytes(cap_of(pix), spp, ds.nlights, nlevels, smp_planes, (size_t)pix * spp);
     };
-    // the free-memory query (a driver round trip) only when the workspace must grow: a
-    // steady frame loop reuses the workspace it already has
-    if (bytes_of(target) > ds.work_bytes) {
-        size_t free_b = 0, total_b = 0;
-        if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) free_b = 0;
-        free_b += ds.work_bytes;  // the current workspace is given back if it is regrown
-        while (target > (1ll << 16) && bytes_of(target) > free_b / 2) target /= 2;
-        if (bytes_of(target) > free_b)
-            throw unsupported_error("max_depth " + std::to_string(A.max_depth) + " needs " +
-                                    std::to_string(bytes_of(target) >> 20) + " MiB of mirror-level records for its " +
-                                    "smallest chunk; " + std::to_string(free_b >> 20) + " MiB of HBM are free");
-    }
-    const int pix_per_chunk = cap_for(target);
+    const int pix_per_chunk = cap_for(chunk_target(ds, A, bytes_of));
     const int seg = seg_of(pix_per_chunk);
     const int cap = cap_of(pix_per_chunk);
     const size_t need = workspace_bytes(cap, spp, ds.nlights, nlevels, smp_planes, (size_t)pix_per_chunk * spp);
-    if (need > ds.work_bytes) {
-        if (ds.work) (void)hipFree(ds.work);
-        ds.work = nullptr;
-        ds.work_bytes = 0;
-        hipError_t e = hipMalloc(&ds.work, need);
-        if (e != hipSuccess) return e;
-        ds.work_bytes = need;
-    }
+    if (hipError_t e = grow_workspace(ds, need); e != hipSuccess) return e;
     wf_buffers B = carve(ds.work, cap, spp, ds.nlights, nlevels);
     B.trel = ds.trel;
     B.seg = seg;
@@ -3005,14 +3044,8 @@ hipError_t run(device_scene& ds, const dev_render_args& A, float4* out, unsigned
         hipError_t e = hipEventCreateWithFlags(&ds.list_stats_ev, hipEventDisableTiming);
         if (e != hipSuccess) return e;
     }
-    if (nlevels > 1 && !ds.level_count_host) {
-        hipError_t e = hipHostMalloc((void**)&ds.level_count_host, sizeof(int) * level_segments * count_stride,
-                                     hipHostMallocDefault);
-        if (e != hipSuccess) return e;
-    }
-    if (nlevels > 1 && !ds.level_count_ev) {
-        hipError_t e = hipEventCreateWithFlags(&ds.level_count_ev, hipEventDisableTiming);
-        if (e != hipSuccess) return e;
+    if (nlevels > 1) {
+        if (hipError_t e = make_level_counts(ds); e != hipSuccess) return e;
     }
     phase_timer& T = ds.timer;
     // LDS staging of the instance tree's top (yrt_scene_set_lds_staging): the persistent walks
@@ -3021,9 +3054,8 @@ hipError_t run(device_scene& ds, const dev_render_args& A, float4* out, unsigned
     ds.last_lds_staging = 0;
     const float4 cam4 = make_float4(A.cam.ox, A.cam.oy, A.cam.oz, 0.0f);
     const int stride_grid = 2048;  // grid-stride kernels: 8 blocks of 256 per CU
-    if (npix_total == 0 && counters) {  // (no chunk, so no k_chunk_setup: the counters still start at 0)
-        hipError_t e = hipMemsetAsync(counters, 0, (size_t)cnt_slots * cnt_count * sizeof(unsigned long long), stream);
-        if (e != hipSuccess) return e;
+    if (npix_total == 0) {  // (no chunk)
+        if (hipError_t e = clear_counters(counters, stream); e != hipSuccess) return e;
     }
     for (long long pix0 = 0; pix0 < npix_total; pix0 += pix_per_chunk) {
         chunk_args C = {pix0, (int)std::min<long long>(pix_per_chunk, npix_total - pix0), spp, tiles_x};
@@ -3055,20 +3087,10 @@ hipError_t run(device_scene& ds, const dev_render_args& A, float4* out, unsigned
         const bool zero_lstats = (B.cam_lists || B.bundles) && !list_stats;
         list_stats |= zero_lstats;
         int t = T.begin(phase_lists, stream);
-        {
-            // the chunk's setup (k_chunk_setup): the camera-relative instance-level records of
-            // this render (the first chunk of a packet render; timed in the lists phase,
-            // YRT_PHASE_LISTS, with the camera lists built from them) and the chunk's zeroed
-            // counters
-            const int nrec = (PACKET && pix0 == 0) ? (int)ds.ntnodes * 2 * spine_len : 0;
-            const int count_ints = nlevels > 1 ? (int)(count_bytes(nlevels) / sizeof(int)) : 0;
-            const int counter_words = pix0 == 0 && counters ? cnt_slots * cnt_count : 0;
-            const int work = std::max(std::max(nrec, count_ints), std::max(counter_words, 32));
-            const int nb = std::min((work + WF_BLOCK - 1) / WF_BLOCK, 1024);
-            hipLaunchKernelGGL(k_chunk_setup, dim3(nb), dim3(WF_BLOCK), 0, stream, nrec ? ds.view.tpair : nullptr,
-                               nrec, A.cam.ox, A.cam.oy, A.cam.oz, ds.trel, B.queue,
-                               zero_lstats ? B.lstats : nullptr, B.count, count_ints, counters, counter_words);
-        }
+        // the camera-relative instance-level records of this render: the first chunk of a packet
+        // render; timed in the lists phase, YRT_PHASE_LISTS, with the camera lists built from them
+        launch_chunk_setup(ds, B, (PACKET && pix0 == 0) ? (int)ds.ntnodes * 2 * spine_len : 0, cam4,
+                           zero_lstats ? B.lstats : nullptr, nlevels, counters, pix0 == 0, stream);
         if (B.cam_lists) {
             const int nt = C.npix / (TILE * TILE);
             hipLaunchKernelGGL(k_camera_lists, dim3((nt + 3) / 4), dim3(256), 0, stream, ds.view, A, C, B);
@@ -3102,21 +3124,18 @@ hipError_t run(device_scene& ds, const dev_render_args& A, float4* out, unsigned
                                    ds.view, A, C, B, counters);
         }
         T.end(t, stream);
-        // levels run: a level with no mirror rays ends the chunk's recursion. The host
-        // reads each level's ray count (written by the previous level's k_shade) without
-        // draining the stream: the level's k_bounce, which takes its count on the device,
-        // is queued first, so the GPU works on it while the count comes back; only a
-        // level that turns out empty costs a launch (one k_bounce of no rays)
+        // levels run: a level with no mirror rays ends the chunk's recursion. The level's
+        // k_bounce is queued before the host waits for the level's ray count, so the GPU
+        // works on it while the count comes back; only a level that turns out empty costs a
+        // launch (one k_bounce of no rays)
         for (int level = 0; level < nlevels; level++) {
             if (level > 0) {
                 t = T.begin(phase_bounce, stream);
                 hipLaunchKernelGGL((k_bounce<COUNT, PACKET, SE>), dim3(stride_grid), dim3(WF_BLOCK), 0, stream, ds.view,
                                    level, B, counters);
                 T.end(t, stream);
-                hipError_t e = hipEventSynchronize(ds.level_count_ev);
-                if (e != hipSuccess) return e;
-                bool any = false;
-                for (int g = 0; g < level_segments; g++) any |= ds.level_count_host[g * count_stride] != 0;
+                bool any;
+                if (hipError_t e = level_has_rays(ds, any); e != hipSuccess) return e;
                 if (!any) break;
             }
             if (ds.nlights > 0) {
@@ -3206,12 +3225,7 @@ hipError_t run(device_scene& ds, const dev_render_args& A, float4* out, unsigned
 #undef YRT_SHADE_LAUNCH
             T.end(t, stream);
             if (level + 1 < nlevels) {
-                hipError_t e = hipMemcpyAsync(ds.level_count_host,
-                                              B.count + (size_t)(level + 1) * level_segments * count_stride,
-                                              sizeof(int) * level_segments * count_stride, hipMemcpyDeviceToHost,
-                                              stream);
-                if (e == hipSuccess) e = hipEventRecord(ds.level_count_ev, stream);
-                if (e != hipSuccess) return e;
+                if (hipError_t e = fetch_level_counts(ds, B, level + 1, stream); e != hipSuccess) return e;
             }
         }
         if (!fuse) {
@@ -3254,47 +3268,22 @@ hipError_t run_rays(device_scene& ds, const dev_render_args& A, const float* ray
                     unsigned long long* counters, hipStream_t stream) {
     constexpr int spp = 1;
     const int nlevels = ds.reflective ? std::max(A.max_depth, 1) : 1;
-    long long target = 1ll << (ds.reflective ? MIRROR_CHUNK_LOG2 : CHUNK_LOG2);
     auto rays_for = [&](long long tgt) { return (int)std::max<long long>(1, std::min<long long>(n, tgt)); };
     // (run()'s slots per sample record: the mirror levels' segments and their slack)
     auto seg_of = [&](int r) { return r / level_segments + level_segments * WF_BLOCK; };
     auto cap_of = [&](int r) { return nlevels > 1 ? level_segments * seg_of(r) : r; };
     auto bytes_of = [&](long long tgt) { return workspace_bytes(cap_of(rays_for(tgt)), spp, ds.nlights, nlevels); };
-    if (bytes_of(target) > ds.work_bytes) {  // (run()'s growth rule)
-        size_t free_b = 0, total_b = 0;
-        if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) free_b = 0;
-        free_b += ds.work_bytes;
-        while (target > (1ll << 16) && bytes_of(target) > free_b / 2) target /= 2;
-        if (bytes_of(target) > free_b)
-            throw unsupported_error("max_depth " + std::to_string(A.max_depth) + " needs " +
-                                    std::to_string(bytes_of(target) >> 20) + " MiB of mirror-level records for its " +
-                                    "smallest chunk; " + std::to_string(free_b >> 20) + " MiB of HBM are free");
-    }
-    const int per_chunk = rays_for(target);
+    const int per_chunk = rays_for(chunk_target(ds, A, bytes_of));
     const int seg = seg_of(per_chunk);
     const int cap = cap_of(per_chunk);
-    const size_t need = workspace_bytes(cap, spp, ds.nlights, nlevels);
-    if (need > ds.work_bytes) {
-        if (ds.work) (void)hipFree(ds.work);
-        ds.work = nullptr;
-        ds.work_bytes = 0;
-        hipError_t e = hipMalloc(&ds.work, need);
-        if (e != hipSuccess) return e;
-        ds.work_bytes = need;
-    }
+    if (hipError_t e = grow_workspace(ds, workspace_bytes(cap, spp, ds.nlights, nlevels)); e != hipSuccess) return e;
     wf_buffers B = carve(ds.work, cap, spp, ds.nlights, nlevels);
     B.seg = seg;
     B.need_v = ds.view.ntextures > 0;
     ds.last_camera_lists = ds.last_bundles = false;
     ds.last_lds_staging = 0;
-    if (nlevels > 1 && !ds.level_count_host) {
-        hipError_t e = hipHostMalloc((void**)&ds.level_count_host, sizeof(int) * level_segments * count_stride,
-                                     hipHostMallocDefault);
-        if (e != hipSuccess) return e;
-    }
-    if (nlevels > 1 && !ds.level_count_ev) {
-        hipError_t e = hipEventCreateWithFlags(&ds.level_count_ev, hipEventDisableTiming);
-        if (e != hipSuccess) return e;
+    if (nlevels > 1) {
+        if (hipError_t e = make_level_counts(ds); e != hipSuccess) return e;
     }
     phase_timer& T = ds.timer;
     const float4 cam4 = make_float4(0.0f, 0.0f, 0.0f, 0.0f);  // (no level takes its view point from a camera)
@@ -3310,16 +3299,7 @@ hipError_t run_rays(device_scene& ds, const dev_render_args& A, const float* ray
         B.rays = rays + (size_t)r0 * 8;
         B.rad = reinterpret_cast<f4*>(out + r0);
         int t = T.begin(phase_lists, stream);
-        {
-            // the chunk's zeroed counters (k_chunk_setup without the camera-relative records)
-            const int count_ints = nlevels > 1 ? (int)(count_bytes(nlevels) / sizeof(int)) : 0;
-            const int counter_words = r0 == 0 && counters ? cnt_slots * cnt_count : 0;
-            const int work = std::max(std::max(count_ints, counter_words), 32);
-            const int nb = std::min((work + WF_BLOCK - 1) / WF_BLOCK, 1024);
-            hipLaunchKernelGGL(k_chunk_setup, dim3(nb), dim3(WF_BLOCK), 0, stream, (const f4*)nullptr, 0, 0.0f, 0.0f,
-                               0.0f, ds.trel, B.queue, (unsigned long long*)nullptr, B.count, count_ints, counters,
-                               counter_words);
-        }
+        launch_chunk_setup(ds, B, 0, cam4, nullptr, nlevels, counters, r0 == 0, stream);  // (no camera-relative records)
         T.end(t, stream);
         t = T.begin(phase_primary, stream);
         hipLaunchKernelGGL((k_rays_first<PACKET, SE>), dim3(grid), dim3(WF_BLOCK), 0, stream, ds.view, nsamp, B,
@@ -3331,10 +3311,8 @@ hipError_t run_rays(device_scene& ds, const dev_render_args& A, const float* ray
                 hipLaunchKernelGGL((k_bounce<false, PACKET, SE>), dim3(stride_grid), dim3(WF_BLOCK), 0, stream, ds.view,
                                    level, B, counters);
                 T.end(t, stream);
-                hipError_t e = hipEventSynchronize(ds.level_count_ev);
-                if (e != hipSuccess) return e;
-                bool any = false;
-                for (int g = 0; g < level_segments; g++) any |= ds.level_count_host[g * count_stride] != 0;
+                bool any;
+                if (hipError_t e = level_has_rays(ds, any); e != hipSuccess) return e;
                 if (!any) break;
             }
             if (ds.nlights > 0) {
@@ -3366,12 +3344,7 @@ hipError_t run_rays(device_scene& ds, const dev_render_args& A, const float* ray
                                    A.max_depth, B, counters);
             T.end(t, stream);
             if (level + 1 < nlevels) {
-                hipError_t e = hipMemcpyAsync(ds.level_count_host,
-                                              B.count + (size_t)(level + 1) * level_segments * count_stride,
-                                              sizeof(int) * level_segments * count_stride, hipMemcpyDeviceToHost,
-                                              stream);
-                if (e == hipSuccess) e = hipEventRecord(ds.level_count_ev, stream);
-                if (e != hipSuccess) return e;
+                if (hipError_t e = fetch_level_counts(ds, B, level + 1, stream); e != hipSuccess) return e;
             }
         }
     }
@@ -3382,9 +3355,7 @@ hipError_t run_rays(device_scene& ds, const dev_render_args& A, const float* ray
 
 hipError_t launch_shade_rays_wavefront(device_scene& ds, const dev_render_args& args, const float* rays, int n,
                                        void* out_rgba, unsigned long long* counters, bool packet, hipStream_t stream) {
-    if (n <= 0)  // (no chunk, so no k_chunk_setup: the counters still start at 0)
-        return counters ? hipMemsetAsync(counters, 0, (size_t)cnt_slots * cnt_count * sizeof(unsigned long long), stream)
-                        : hipSuccess;
+    if (n <= 0) return clear_counters(counters, stream);  // (no chunk)
     float4* out = (float4*)out_rgba;
     if (packet) return run_rays<true, uint32_t>(ds, args, rays, n, out, counters, stream);
     if (ds.narrow_stack) return run_rays<false, uint16_t>(ds, args, rays, n, out, counters, stream);
@@ -3393,11 +3364,8 @@ hipError_t launch_shade_rays_wavefront(device_scene& ds, const dev_render_args& 
 
 hipError_t launch_render_wavefront(device_scene& ds, const dev_render_args& args, void* out_rgba,
                                    unsigned long long* counters, bool count_work, bool packet, hipStream_t stream) {
-    // an empty window (a band offset without bands): no chunk, so no k_chunk_setup -- the
-    // counters still start at 0, or yrt_last_stats would report the render before this one
-    if (args.tile_w <= 0 || args.tile_h <= 0)
-        return counters ? hipMemsetAsync(counters, 0, (size_t)cnt_slots * cnt_count * sizeof(unsigned long long), stream)
-                        : hipSuccess;
+    // an empty window (a band offset without bands): no chunk
+    if (args.tile_w <= 0 || args.tile_h <= 0) return clear_counters(counters, stream);
     float4* out = (float4*)out_rgba;
     if (packet) {
         // the per-wave stack holds 32-bit node indices: no narrow/wide split needed
@@ -3414,9 +3382,7 @@ hipError_t launch_render_wavefront(device_scene& ds, const dev_render_args& args
 hipError_t launch_render_wavefront_passes(device_scene& ds, const dev_render_args& args, unsigned mask,
                                           const dev_pass_planes& out, void* beauty_rgba, unsigned long long* counters,
                                           bool packet, hipStream_t stream) {
-    if (args.tile_w <= 0 || args.tile_h <= 0)  // (an empty window: as launch_render_wavefront)
-        return counters ? hipMemsetAsync(counters, 0, (size_t)cnt_slots * cnt_count * sizeof(unsigned long long), stream)
-                        : hipSuccess;
+    if (args.tile_w <= 0 || args.tile_h <= 0) return clear_counters(counters, stream);  // (an empty window)
     pass_buffers P = {};
     P.mask = (mask & ((1u << pass_count) - 1)) | (beauty_rgba ? 1u << pass_count : 0u);
     for (int k = 0; k < pass_count; k++) P.out[k] = (mask >> k & 1) ? (float4*)out.plane[k] : nullptr;
