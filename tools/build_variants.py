@@ -49,12 +49,23 @@ TEST_VARIANTS = {
 }
 
 
+# knobs kept for A/B against the default (tools/ab_variants.py) that the suite compares with it
+# on a few frames of their own instead of running all of tests/test_gpu_variants.py's cases:
+# the item paths' emulated divisions and per-item range checks, and the fused grid's shading
+# computing each light's direction and distance again (tests/test_gpu_item_geometry_variants.py)
+KNOB_VARIANTS = {
+    "itemdiv": ["-DYRT_ITEM_MAGIC=0"],
+    "nocarry": ["-DYRT_LIGHT_CARRY=0"],
+}
+
+
 def library_path(name: str) -> Path:
     return OUT_DIR / f"libyrt_{name}.so"
 
 
 def test_specs() -> list:
-    return [f"{name}:{','.join(defs)}" for name, defs in TEST_VARIANTS.items()]
+    """every library the suite loads: TEST_VARIANTS first, in their order, then KNOB_VARIANTS"""
+    return [f"{name}:{','.join(defs)}" for name, defs in (*TEST_VARIANTS.items(), *KNOB_VARIANTS.items())]
 
 
 def _sources_digest() -> str:

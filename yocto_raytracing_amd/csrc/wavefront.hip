@@ -35,6 +35,7 @@
 #include <stdexcept>
 #include <type_traits>
 
+#include "item_magic.h"
 #include "packet_trace.h"
 #include "trace_common.h"
 #include "yrt_render.h"
@@ -148,11 +149,20 @@ __device__ __forceinline__ int* seg_counter(int* count, int level, int g) {
     return count + (level * level_segments + g) * count_stride;
 }
 
+#if !defined(YRT_ITEM_MAGIC)  // (its non-default build is the `itemdiv` library of tools/build_variants.py)
+// the item paths' divisions by spp, samples, tiles_x and band as a multiply-high and shifts
+// (item_magic.h, the pairs made once per frame by run()), the item's tile on the scalar unit
+// where an item lies in one tile, and camera_ray_w's range checks decided once per frame
+// (DESIGN.md §5); 0: the emulated divisions and the per-item ballots
+#define YRT_ITEM_MAGIC 1
+#endif
+
 struct chunk_args {
     long long pix0;  // first pixel (in tile enumeration order) of this chunk
     int npix;        // pixels in this chunk
     int spp;
     int tiles_x;     // 8x8 tiles across the window
+    item_magic M;    // (YRT_ITEM_MAGIC) the frame's division pairs; all zero: the general code
 };
 
 // pixel enumeration: 8x8 tiles across the local window, row-major tiles, row-major
@@ -168,6 +178,35 @@ __device__ __forceinline__ bool pixel_of(const dev_render_args& A, int tiles_x, 
     int b = ly / A.band, r = ly % A.band;
     j = A.y0 + (b * A.band_stride + A.band_offset) * A.band + r;
     return i < A.width && j < A.height;
+}
+
+// pixel w of tile t, with the frame's pairs (C.M.on). t and w may be wave-uniform: the
+// caller hands the pairs' words over as it holds them (scalars there, lanes elsewhere)
+struct tile_magic {
+    uint32_t tx_mul, tx_shift, tiles_x, band_mul, band_shift, band;
+};
+__device__ __forceinline__ bool pixel_of_tile(const dev_render_args& A, const tile_magic& G, uint32_t t, uint32_t w,
+                                              int& lx, int& ly, int& i, int& j) {
+    const uint32_t ty = magic_div(t, G.tx_mul, G.tx_shift), tx = t - ty * G.tiles_x;
+    lx = (int)(tx * TILE + (w % TILE));
+    ly = (int)(ty * TILE + (w / TILE));
+    if (lx >= A.tile_w || ly >= A.tile_h) return false;
+    i = A.x0 + lx;
+    const uint32_t b = magic_div((uint32_t)ly, G.band_mul, G.band_shift), r = (uint32_t)ly - b * G.band;
+    j = A.y0 + ((int)b * A.band_stride + A.band_offset) * A.band + (int)r;
+    return i < A.width && j < A.height;
+}
+__device__ __forceinline__ tile_magic tile_magic_of(const chunk_args& C) {
+    return {C.M.tiles_x.mul, C.M.tiles_x.shift, C.M.tiles_x.d, C.M.band.mul, C.M.band.shift, C.M.band.d};
+}
+// pixel_of for the callers that hold the chunk's arguments: the pairs where the frame has them
+__device__ __forceinline__ bool pixel_of(const dev_render_args& A, const chunk_args& C, long long p, int& lx,
+                                         int& ly, int& i, int& j) {
+    if (YRT_ITEM_MAGIC && C.M.on) {  // (uniform over the grid)
+        const uint32_t p32 = (uint32_t)p;
+        return pixel_of_tile(A, tile_magic_of(C), p32 / (TILE * TILE), p32 % (TILE * TILE), lx, ly, i, j);
+    }
+    return pixel_of(A, C.tiles_x, p, lx, ly, i, j);
 }
 
 __device__ __forceinline__ void flush(unsigned long long* counters, int idx, unsigned long long v) {
@@ -453,19 +492,21 @@ __device__ __forceinline__ bool light_term_zero(int info, vec3f nrm, vec3f p, ve
 
 // camera_ray (trace_common.h, raytrace.cpp:6-37 with the uv of :235-238) with its four
 // divisions and normalize through fast_div.h where every active lane is in range (the
-// same bits); called per lane in divergent code (the checks ballot the active lanes)
+// same bits); called per lane in divergent code (the checks ballot the active lanes).
+// in_range (wave-uniform): run() has decided for the whole frame that every division is in
+// range (item_magic::div_ok), so the checks are not made
 __device__ __forceinline__ ray3 camera_ray_w(const dev_camera& cam, int W, int H, int ns, int i, int j, int ii,
-                                             int jj) {
+                                             int jj, bool in_range = false) {
     const float fns = (float)ns, fw = (float)W, fh = (float)H;
     const float a = ii + 0.5f, b = jj + 0.5f;
     float u, v;
-    if (YRT_FAST_NORMALIZE && !__ballot(!(div_nr_ok(a, fns) && div_nr_ok(b, fns)))) {
+    if (YRT_FAST_NORMALIZE && (in_range || !__ballot(!(div_nr_ok(a, fns) && div_nr_ok(b, fns))))) {
         const float y = rcp_nr(fns);
         u = i + div_nr(a, fns, y), v = j + div_nr(b, fns, y);
     } else {
         u = i + a / fns, v = j + b / fns;
     }
-    if (YRT_FAST_NORMALIZE && !__ballot(!(div_nr_ok(u, fw) && div_nr_ok(v, fh)))) {
+    if (YRT_FAST_NORMALIZE && (in_range || !__ballot(!(div_nr_ok(u, fw) && div_nr_ok(v, fh))))) {
         u = div_nr(u, fw, rcp_nr(fw)), v = div_nr(v, fh, rcp_nr(fh));
     } else {
         u = u / fw, v = v / fh;
@@ -621,7 +662,43 @@ __device__ __forceinline__ bool primary_samples(const dev_scene_view& S, const d
     const int nsamp = C.npix * C.spp;
     bool valid = false;
     ray3 ray = {{0, 0, 0}, {0, 0, 1}, ray_eps, flt_max};
-    if (idx < nsamp) {
+    const bool magic = YRT_ITEM_MAGIC && uniform(C.M.on) != 0;
+    int list_tile = -1;  // (magic) wave-uniform: the chunk's tile all of the wave's samples lie in
+    if (magic) {
+        const bool in_range = uniform(C.M.div_ok) != 0;
+        const int ns = A.samples;
+        int lx, ly, i, j, ii, jj;
+        if (uniform(C.M.pow2)) {
+            // an item is 64 / spp whole pixels of one tile (pix0 is whole tiles): the tile, and
+            // at 64 spp the pixel, from the item index on the scalar unit; the lane's pixel and
+            // sample are bits of its index
+            const uint32_t item = (uint32_t)uniform(idx) >> 6;
+            const uint32_t sl = (uint32_t)uniform(C.M.spp_log2), lane = (uint32_t)idx & 63u;
+            const uint32_t ct = item >> sl;  // the tile of the chunk
+            const uint32_t t = (uint32_t)uniform((int)(uint32_t)(C.pix0 >> 6)) + ct;
+            const tile_magic G = {(uint32_t)uniform((int)C.M.tiles_x.mul), (uint32_t)uniform((int)C.M.tiles_x.shift),
+                                  (uint32_t)uniform((int)C.M.tiles_x.d),  (uint32_t)uniform((int)C.M.band.mul),
+                                  (uint32_t)uniform((int)C.M.band.shift), (uint32_t)uniform((int)C.M.band.d)};
+            const uint32_t w0 = (item & ((1u << sl) - 1u)) << (6u - sl);  // the item's first pixel in the tile
+            if (sl == 6u)
+                valid = pixel_of_tile(A, G, t, w0, lx, ly, i, j);
+            else
+                valid = pixel_of_tile(A, G, t, w0 + (lane >> sl), lx, ly, i, j);
+            const uint32_t q = lane & ((1u << sl) - 1u), nl = sl >> 1;
+            ii = (int)(q & ((1u << nl) - 1u)), jj = (int)(q >> nl);
+            valid = valid && idx < nsamp;
+            if ((int)(item * 64u) < nsamp) list_tile = (int)ct;
+        } else {
+            const uint32_t pl = magic_div((uint32_t)idx, C.M.spp), q = (uint32_t)idx - pl * (uint32_t)C.spp;
+            const uint32_t p = (uint32_t)C.pix0 + pl;
+            valid = idx < nsamp && pixel_of_tile(A, tile_magic_of(C), p / (TILE * TILE), p % (TILE * TILE), lx, ly, i, j);
+            jj = (int)magic_div(q, C.M.samples), ii = (int)q - jj * ns;
+        }
+        if (valid)
+            ray = camera_ray_w(A.cam, A.width, A.height, ns, i, j, ii, jj, in_range);
+        else if (idx < nsamp)
+            store_not_sample(B, idx);
+    } else if (idx < nsamp) {
         const long long p = C.pix0 + idx / C.spp;
         const int q = idx % C.spp;
         int lx, ly, i, j;
@@ -645,7 +722,16 @@ __device__ __forceinline__ bool primary_samples(const dev_scene_view& S, const d
         if (LIST && !COUNT) {
             const int nsamp = C.npix * C.spp;
             const int i0 = uniform(idx) & ~63, i1 = min(i0 + 63, nsamp - 1);
-            const int t0 = i0 / C.spp / (TILE * TILE), t1 = i1 / C.spp / (TILE * TILE);
+            int t0, t1;
+            if (magic && list_tile >= 0) {
+                t0 = t1 = list_tile;
+            } else if (magic) {  // (scalar: the sample indices and the pair are wave-uniform)
+                const uint32_t mul = (uint32_t)uniform((int)C.M.spp.mul), sh = (uint32_t)uniform((int)C.M.spp.shift);
+                t0 = (int)(magic_div((uint32_t)i0, mul, sh) / (TILE * TILE));
+                t1 = (int)(magic_div((uint32_t)max(i1, 0), mul, sh) / (TILE * TILE));
+            } else {
+                t0 = i0 / C.spp / (TILE * TILE), t1 = i1 / C.spp / (TILE * TILE);
+            }
             // (a zero direction -- a camera with no extent -- walks the tree)
             const bool zero_dir = valid && ray.d.x == 0.0f && ray.d.y == 0.0f && ray.d.z == 0.0f;
             if (t0 == t1 && i0 < nsamp && !ballot(zero_dir)) {
@@ -1897,7 +1983,7 @@ template <int LDSN, bool IL, bool WCULL = false>
 __device__ __forceinline__ bool shadow_item_light(const dev_scene_view& S, const wf_buffers& B, int nsamp, int bx,
                                                   int li, int nl, unsigned lane, const vec3f& cam_o,
                                                   const float4* lds_nodes, unsigned& rays, unsigned& culled_n,
-                                                  bool& valid) {
+                                                  bool& valid, float4* carry = nullptr) {
     // the light's frame and position: one wave-uniform record, through the scalar cache
     float4 lrec[6];
     ld_records_at<6>(S.lights, (unsigned)(6 * li), lrec);
@@ -1922,6 +2008,8 @@ __device__ __forceinline__ bool shadow_item_light(const dev_scene_view& S, const
             normalize_len(tp, l, r);
             sr = {p, l, 0.01f, r - 0.01f};
             valid = true;
+            // (YRT_LIGHT_CARRY) for the item's shading, which would compute both again
+            if (carry) carry[lane] = make_float4(l.x, l.y, l.z, r);
         }
     }
     rays += (unsigned)__popcll(ballot(valid));
@@ -2114,7 +2202,11 @@ __device__ __forceinline__ void shade_hit(const dev_scene_view& S, const wf_buff
                                           int max_depth, const AMB& amb, const float* lut, work_counts& wc,
                                           unsigned long long& truncated, vec3f& R, vec3f& p, bool& spawn, vec3f& dr,
                                           vec3f& rec_d, vec3f& rec_la, int& rec_mat, bool& write_r,
-                                          TERMS* terms = nullptr) {
+                                          TERMS* terms = nullptr, const float4* carried = nullptr,
+                                          int ncarried = 0) {
+    // carried (k_shadow_shade_persist, YRT_LIGHT_CARRY): this lane's {l, r} of light li at
+    // carried[li * 64], for li < ncarried -- the values the light loop computes, from the same
+    // statements on the same p (shadow_item_light)
     constexpr bool SPLIT = !std::is_same<TERMS, no_terms>::value;
     vec3f nrm;
     vec2f uv;
@@ -2156,14 +2248,24 @@ __device__ __forceinline__ void shade_hit(const dev_scene_view& S, const wf_buff
         const f4* lr = S.lights + 6 * li;
         // the light record is the same for every lane (li is the loop index):
         // one scalar fetch instead of six 64-lane vector loads of one address
-        float4 lrec[6];
-        ld_scalar<6>(lr, lrec);
-        frame3f lf = {xyz(lrec[0]), xyz(lrec[1]), xyz(lrec[2]), xyz(lrec[3])};
-        vec3f lp0 = xyz(lrec[4]), ke = xyz(lrec[5]);
-        vec3f tp = transform_point(lf, lp0 - p);
-        vec3f l, h;
+        vec3f l, h, ke;
         float r, hlen;
-        normalize_len(tp, l, r);
+        if (carried && li < ncarried) {
+            // (YRT_LIGHT_CARRY) the light step of this item left the sample's {l, r} in LDS
+            float4 lrec[2];
+            ld_scalar_at<2>(S.lights, (unsigned)(6 * li + 4), lrec);
+            ke = xyz(lrec[1]);
+            const float4 c4 = carried[li * 64];
+            l = xyz(c4), r = c4.w;
+        } else {
+            float4 lrec[6];
+            ld_scalar<6>(lr, lrec);
+            frame3f lf = {xyz(lrec[0]), xyz(lrec[1]), xyz(lrec[2]), xyz(lrec[3])};
+            vec3f lp0 = xyz(lrec[4]);
+            ke = xyz(lrec[5]);
+            vec3f tp = transform_point(lf, lp0 - p);
+            normalize_len(tp, l, r);
+        }
         normalize_len(v + l, h, hlen);
         vec3f kd = kd0, ks = ks0;
         if (kd_txt >= 0) kd = kd * tkd;
@@ -2229,7 +2331,7 @@ __device__ __forceinline__ void sum_pixels(const dev_render_args& A, const chunk
         const int px = t / 3, comp = t - 3 * px;
         const int pl = pl0 + px;
         int lx, ly, i, j;
-        const bool valid = pl < C.npix && pixel_of(A, C.tiles_x, C.pix0 + pl, lx, ly, i, j);
+        const bool valid = pl < C.npix && pixel_of(A, C, C.pix0 + pl, lx, ly, i, j);
         if (pl < C.npix && lx < A.tile_w && ly < A.tile_h) {
             float v = 0.0f;
             if (valid) {
@@ -2615,7 +2717,7 @@ __global__ __launch_bounds__(SB, FUSE ? shade_pass_waves : YRT_SHADE_LEVEL_WAVES
             if (!(P.mask >> k & 1)) continue;
             const int pl = (int)(blockIdx.x * SB / C.spp) + px;
             int lx, ly, i, j;
-            const bool valid = pl < C.npix && pixel_of(A, C.tiles_x, C.pix0 + pl, lx, ly, i, j);
+            const bool valid = pl < C.npix && pixel_of(A, C, C.pix0 + pl, lx, ly, i, j);
             if (pl < C.npix && lx < A.tile_w && ly < A.tile_h) {
                 float v = 0.0f;
                 if (valid) {
@@ -2650,6 +2752,12 @@ __global__ __launch_bounds__(SB, FUSE ? shade_pass_waves : YRT_SHADE_LEVEL_WAVES
 #else
 #define YRT_SHADOW_SHADE_KERNEL 0
 #endif
+#if !defined(YRT_LIGHT_CARRY)
+// k_shadow_shade_persist: each of an item's first four lights leaves its {l, r} per lane in LDS for
+// the item's shading, which then does not redo transform_point + normalize_len per unoccluded
+// light; 0: shade_hit computes them again
+#define YRT_LIGHT_CARRY 1
+#endif
 #if (YRT_SHADOW_SHADE_KERNEL)
 // k_shadow_persist<0>'s item loop with the answers kept as one bit per light and lane, then
 // per item k_shade<fused>'s body: shade_hit for the lane's sample, the 64 values through a
@@ -2663,7 +2771,11 @@ __global__ __launch_bounds__(SP_BLOCK, YRT_SHADOW_WAVES) void k_shadow_shade_per
                                                                                       float4* __restrict__ out) {
     constexpr int WPB = SP_BLOCK / 64;  // waves per block
     constexpr unsigned RUN = YRT_SHADOW_ITEM_RUN;
-    __shared__ float4 wave_rad[WPB][64];
+    // per wave: the item's 64 radiance values for sum_pixels, and (YRT_LIGHT_CARRY) ahead of them,
+    // in the same rows, each of the first CARRY lights' {l, r} per lane from its light step to the
+    // item's shading: row 0 is written as radiance once the shading has read it
+    constexpr int CARRY = YRT_LIGHT_CARRY ? 4 : 0;
+    __shared__ float4 wave_slab[WPB][CARRY ? CARRY : 1][64];
     __shared__ unsigned wave_truncated[WPB];  // (in LDS: a register would be live across the walks)
     __shared__ srgb_table srgb_lds;
     // the epilogue reads the frame's and the chunk's arguments from an LDS copy, per item: as
@@ -2712,7 +2824,7 @@ __global__ __launch_bounds__(SP_BLOCK, YRT_SHADOW_WAVES) void k_shadow_shade_per
         for (int li = 0; li < nl; li++) {
             bool valid;
             const bool occ = shadow_item_light<0, true, true>(S, B, nsamp, bx, li, nl, lane_now(), cam_o, nullptr, rays,
-                                                              culled, valid);
+                                                              culled, valid, li < CARRY ? wave_slab[w][li] : nullptr);
             occ_bits |= (occ ? 1u : 0u) << li;
         }
         // the item's samples are shaded (k_shade<fused>'s body for one sample) ...
@@ -2730,7 +2842,8 @@ __global__ __launch_bounds__(SP_BLOCK, YRT_SHADOW_WAVES) void k_shadow_shade_per
                 int rec_mat = 0;
                 bool spawn = false, write_r = true;
                 shade_hit<false, true, true, true>(S, B, idx, info, s0, ro4, occ_bits, 0, 1, amb, lut, wc, truncated, R, p,
-                                             spawn, dr, rec_d, rec_la, rec_mat, write_r);
+                                             spawn, dr, rec_d, rec_la, rec_mat, write_r, (no_terms*)nullptr,
+                                             CARRY ? &wave_slab[w][0][lane_now()] : nullptr, CARRY);
             }
         }
         const unsigned lane = lane_now();
@@ -2738,15 +2851,15 @@ __global__ __launch_bounds__(SP_BLOCK, YRT_SHADOW_WAVES) void k_shadow_shade_per
         if (ntrunc && lane == 0) wave_truncated[w] += ntrunc;
         // ... and its pixels summed from the wave's own slab: the wave's LDS operations complete
         // in order, the waits keep the compiler from moving them across each other
-        wave_rad[w][lane] = make_float4(R.x, R.y, R.z, 1.0f);
+        wave_slab[w][0][lane] = make_float4(R.x, R.y, R.z, 1.0f);
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // every lane's value, before any lane sums
         // (one pixel per item, 64 spp, is the long chain: 64 dependent adds per item)
         const int spp = __builtin_amdgcn_readfirstlane(args.C.spp);
         if (spp == 64) {
-            sum_pixels<64, 64>(args.A, args.C, out, wave_rad[w], bx, 1, (int)lane);
+            sum_pixels<64, 64>(args.A, args.C, out, wave_slab[w][0], bx, 1, (int)lane);
         } else {
             const int sl = __builtin_ctz((unsigned)spp);  // (spp divides 64: a power of two)
-            sum_pixels<64>(args.A, args.C, out, wave_rad[w], bx << (6 - sl), 64 >> sl, (int)lane);
+            sum_pixels<64>(args.A, args.C, out, wave_slab[w][0], bx << (6 - sl), 64 >> sl, (int)lane);
         }
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // the sums' reads, before the next item's values
     }
@@ -2796,7 +2909,7 @@ __device__ __forceinline__ void accumulate_plane(dev_render_args A, chunk_args C
     if (lane >= np) return;
     const int pl = pl0 + lane;
     int lx, ly, i, j;
-    const bool valid = pixel_of(A, C.tiles_x, C.pix0 + pl, lx, ly, i, j);
+    const bool valid = pixel_of(A, C, C.pix0 + pl, lx, ly, i, j);
     if (lx >= A.tile_w || ly >= A.tile_h) return;
     const float d = float(C.spp);
     out()[(size_t)ly * A.out_stride + lx] =
@@ -3018,6 +3131,10 @@ hipError_t run(device_scene& ds, const dev_render_args& A, float4* out, unsigned
     const int pix_per_chunk = cap_for(chunk_target(ds, A, bytes_of));
     const int seg = seg_of(pix_per_chunk);
     const int cap = cap_of(pix_per_chunk);
+    // the frame's division pairs and range decisions, the same for every chunk (item_magic.h)
+    const item_magic M = make_item_magic(spp, A.samples, tiles_x, A.band, (uint64_t)npix_total,
+                                         (uint64_t)pix_per_chunk * spp, (uint64_t)tiles_y * TILE, A.width, A.height,
+                                         A.x0, A.y0);
     const size_t need = workspace_bytes(cap, spp, ds.nlights, nlevels, smp_planes, (size_t)pix_per_chunk * spp);
     if (hipError_t e = grow_workspace(ds, need); e != hipSuccess) return e;
     wf_buffers B = carve(ds.work, cap, spp, ds.nlights, nlevels);
@@ -3059,6 +3176,7 @@ hipError_t run(device_scene& ds, const dev_render_args& A, float4* out, unsigned
     }
     for (long long pix0 = 0; pix0 < npix_total; pix0 += pix_per_chunk) {
         chunk_args C = {pix0, (int)std::min<long long>(pix_per_chunk, npix_total - pix0), spp, tiles_x};
+        if (YRT_ITEM_MAGIC) C.M = M;
         const int nsamp = C.npix * spp;
         const int grid = (nsamp + WF_BLOCK - 1) / WF_BLOCK;
         constexpr int TB = shadow_block<PACKET>();
