@@ -1,4 +1,4 @@
-"""The list builders' instance masks (YRT_INSTANCE_MASKS): k_camera_lists
+"""The list builders' instance masks: k_camera_lists
 and k_bundle_lists mark the instances of a listed leaf whose world box (dev_scene_view ibox)
 their cone or hull excludes, drop leaves whose every instance is excluded, and the walks pass
 over the marked instances. Exact only if the world box holds everything the instance's

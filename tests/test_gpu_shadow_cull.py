@@ -1,5 +1,5 @@
-"""Shadow rays whose light term is exactly zero are not traced (wavefront.hip light_term_zero,
-YRT_SHADOW_CULL): the light's term in shade() (raytrace.cpp:133-183) is +-0 for a hit facing
+"""Shadow rays whose light term is exactly zero are not traced (wavefront.hip
+light_term_zero): the light's term in shade() (raytrace.cpp:133-183) is +-0 for a hit facing
 away from the light on a material without specular (class 1) or with an exponent high enough
 that pow(max(0, n.h), ns) is exactly 0 (classes >= 2), so the occlusion cannot change the
 pixel. These scenes put every material class, and the cases that must NOT be culled, in one

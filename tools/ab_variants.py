@@ -121,7 +121,7 @@ def main():
             print(name, "work", {f: getattr(s, f) for f, _ in N.Stats._fields_})
     summary = {}
     for name, d in res.items():
-        summary[name] = {ph: {"median": statistics.median(v), "min": min(v)} for ph, v in d.items()}
+        summary[name] = {ph: {"median": statistics.median(v), "min": min(v), "max": max(v)} for ph, v in d.items()}
         print(name, {ph: round(v["median"], 2) for ph, v in summary[name].items()}, "image", digest[name])
     print(json.dumps(summary))
 

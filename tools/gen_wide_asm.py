@@ -14,8 +14,7 @@ the others are pushed highest first so that they pop in slot order), the leaf te
 next item, and the pops (stack entries keep their lane masks: a popped 4-wide entry is not
 tested again, so its mask is the result of its box test at the parent).
 
-The computation is wide_descend<OCT, 0>'s with YRT_ANY_CONSERVATIVE off: the same slab
-tests (box_oct), the same order. The block clobbers s16-s31 and s36-s55 (the record, the slot
+The computation is wide_descend<OCT, 0>'s: the same slab tests (box_oct), the same order. The block clobbers s16-s31 and s36-s55 (the record, the slot
 masks), VCC, M0 and SCC. It exits with mask != 0 and cur a leaf word, or mask = 0 when the level is done.
 """
 from __future__ import annotations

@@ -487,14 +487,10 @@ __device__ __forceinline__ int wave_octant(vec3f invd, unsigned long long lanes)
     return (nx ? 1 : 0) | (ny ? 2 : 0) | (nz ? 4 : 0);
 }
 
-#ifndef YRT_POP_ONE_EXIT
-#define YRT_POP_ONE_EXIT 1
-#endif
 // pop inside a descent: entries above `floor` until one with live lanes (true), or down
 // to the floor (false, mask 0) -- the level boundary is the caller's
 __device__ __forceinline__ bool inner_pop(int floor, unsigned long long done, int& node, unsigned long long& mask,
                                           int& sp, int stk_node, int stk_mlo, int stk_mhi) {
-#if YRT_POP_ONE_EXIT
     // one exit block: the loop leaves through the same edge whether it found live lanes or
     // reached the floor, and the empty asm hides m from the optimiser so that it cannot thread
     // the caller's test back into the loop (two exit blocks make the structurizer's
@@ -512,18 +508,6 @@ __device__ __forceinline__ bool inner_pop(int floor, unsigned long long done, in
     asm volatile("" : "+s"(m));
     mask = m;
     return m != 0;
-#else
-    while (sp > floor) {
-        sp--;
-        node = __builtin_amdgcn_readlane(stk_node, sp);
-        mask = ((unsigned long long)(uint32_t)__builtin_amdgcn_readlane(stk_mhi, sp) << 32 |
-                (uint32_t)__builtin_amdgcn_readlane(stk_mlo, sp)) &
-               ~done;
-        if (mask) return true;
-    }
-    mask = 0;
-    return false;
-#endif
 }
 
 // The closest hit's stack without lane masks (YRT_STACK_MASKS 0): an entry is the node
@@ -566,14 +550,7 @@ __device__ __forceinline__ bool inner_pop_avail(int floor, unsigned long long av
     return m != 0;
 }
 
-constexpr int packet_block = 256;
-#ifndef YRT_R5_LANE
-#define YRT_R5_LANE 1
-#endif
-#ifndef YRT_R5_UORIG
-#define YRT_R5_UORIG 1
-#endif  // >= threads per block of every kernel that runs packet_first
-
+constexpr int packet_block = 256;  // >= threads per block of every kernel that runs packet_first
 
 // one descent of the closest-hit walk from the spine record at byte offset `node` of
 // pbase: returns with mask = 0 when no lane passes, or with a leaf reached (mask: its
@@ -590,14 +567,6 @@ constexpr int packet_block = 256;
 // LDSN > 0 (REL only): the first LDSN records of pbase are also in `lds` (staged per block by
 // k_primary_persist, YRT_PRIMARY_LDS_RECORDS); a record below that offset is read with
 // ds_read_b128 at a wave-uniform address instead of through the scalar cache
-#ifndef YRT_DESCENT_ONE_EXIT
-#define YRT_DESCENT_ONE_EXIT 1
-#endif
-#if YRT_DESCENT_ONE_EXIT
-#define YRT_DESCENT_EXIT break
-#else
-#define YRT_DESCENT_EXIT return
-#endif
 //
 // SM: the stack holds lane masks (`done`: the lanes that left the walk); without them
 // (inner_pop_avail) `done` is the level's available lanes instead
@@ -658,13 +627,13 @@ __device__ __forceinline__ void first_descend(const f4* pbase, vec3f co, vec3f c
         mask = pm0;
         if (!pm0) {
             if (YRT_POP) continue;
-            YRT_DESCENT_EXIT;
+            break;
         }
         const int s0 = uniform(ibits(rec[0].w));
         const uint32_t c0 = (uint32_t)uniform(ibits(rec[1].w));
         if (c0 & leaf_bit) {
             node = s0, cl = c0;
-            YRT_DESCENT_EXIT;
+            break;
         }
         // push L (X's child start) for the lanes that passed X
         stk_node = writelane(stk_node, s0, sp);
@@ -678,13 +647,13 @@ __device__ __forceinline__ void first_descend(const f4* pbase, vec3f co, vec3f c
         mask = pm1;
         if (!pm1) {
             if (YRT_POP) continue;
-            YRT_DESCENT_EXIT;
+            break;
         }
         const int s1 = uniform(ibits(rec[2].w));
         const uint32_t c1 = (uint32_t)uniform(ibits(rec[3].w));
         if (c1 & leaf_bit) {
             node = s1, cl = c1;
-            YRT_DESCENT_EXIT;
+            break;
         }
         // push RL (R's child start)
         stk_node = writelane(stk_node, s1, sp);
@@ -696,7 +665,6 @@ __device__ __forceinline__ void first_descend(const f4* pbase, vec3f co, vec3f c
         node = s1 + spine_record_bytes;
     }
 #undef YRT_POP
-#if YRT_DESCENT_ONE_EXIT
     // every exit of the loop above arrives here; the empty asm makes the exit state opaque so
     // that the caller's tests on it (leaf reached or not) are not threaded back into the loop
     // as separate exit blocks
@@ -707,9 +675,7 @@ __device__ __forceinline__ void first_descend(const f4* pbase, vec3f co, vec3f c
     node = uniform(node);
     cl = (uint32_t)uniform((int)cl);
     asm volatile("" : "+s"(mask), "+s"(node), "+s"(cl));
-#endif
 }
-#undef YRT_DESCENT_EXIT
 
 // ---- closest hit, laid out for the scalar unit ----
 // The packet discipline of packet_any (same node tests, in the reference's order, with
@@ -752,14 +718,14 @@ __device__ __forceinline__ bool packet_first(const dev_scene_view& S, const ray3
     static_assert(spine_len == 2, "packet_first walks two-node spine records");
     // (this lane's bit, wave-relative LDS slot: recomputed where used -- lane_now() is not
     // hoisted out of a persistent caller's item loop, where a held copy would be spilled)
-    const unsigned long long me = (COUNT || !YRT_R5_LANE) ? 1ull << __lane_id() : 0ull;
+    const unsigned long long me = COUNT ? 1ull << __lane_id() : 0ull;
     const unsigned long long live = ballot(valid && !is_nan(wray.tmin) && !is_nan(wray.tmax));
     if (!live) return false;
     // REL: every live lane's ray starts at the one origin the records were made relative to
     // (the camera's): it is read from the first live lane into SGPRs, so the walk holds no
     // VGPRs for it
     const int fl = __builtin_ctzll(live);
-    const vec3f wo = (REL && YRT_R5_UORIG) ? vec3f{__int_as_float(__builtin_amdgcn_readlane(__float_as_int(wray.o.x), fl)),
+    const vec3f wo = REL ? vec3f{__int_as_float(__builtin_amdgcn_readlane(__float_as_int(wray.o.x), fl)),
                                  __int_as_float(__builtin_amdgcn_readlane(__float_as_int(wray.o.y), fl)),
                                  __int_as_float(__builtin_amdgcn_readlane(__float_as_int(wray.o.z), fl))}
                          : wray.o;
@@ -772,7 +738,7 @@ __device__ __forceinline__ bool packet_first(const dev_scene_view& S, const ray3
     __shared__ float wi_lds[3][BS];
     const int wave = uniform((int)threadIdx.x >> 6);
     {
-        const int t = YRT_R5_LANE ? wave * 64 + lane_now() : (int)threadIdx.x;
+        const int t = wave * 64 + lane_now();
         wi_lds[0][t] = ci.x, wi_lds[1][t] = ci.y, wi_lds[2][t] = ci.z;
     }
     float hw1 = 0, hw2 = 0;
@@ -1030,7 +996,7 @@ __device__ __forceinline__ bool packet_first(const dev_scene_view& S, const ray3
                 co = wo;
                 cd = wd;
                 {
-                    const int t = YRT_R5_LANE ? wave * 64 + lane_now() : (int)threadIdx.x;
+                    const int t = wave * 64 + lane_now();
                     ci = {wi_lds[0][t], wi_lds[1][t], wi_lds[2][t]};
                 }
                 oct = woct;
@@ -1101,84 +1067,17 @@ __device__ __forceinline__ void ld_wide_record(const f4* wbase, uint32_t off, fl
     r[4] = rec_of(b, 0), r[5] = rec_of(b, 1), r[6] = rec_of(c, 0);
 }
 
-// ---- a cheaper slab test for the any-hit walk's inner slots ----
-// Any hit does not depend on the order of the walk, only on which leaves are reached, and
-// the reference reaches a leaf exactly when the leaf's own box passes intersect_check_bbox
-// (scene.cpp:371-382): its ancestors' boxes contain it and the test is monotone in the box
-// (the argument of the 4-wide collapse, packet_occluded_wide2). So an inner slot may use
-// any test that passes at least every ray the exact one passes; leaf slots keep the exact
-// test, and the set of leaves reached -- and so the answer -- stays the reference's.
-//
-// The inner test computes each plane distance as one FMA, fma(b, invd, -(o * invd)), instead
-// of (b - o) * invd (a subtraction and a product), and widens the comparison by the error
-// of that form. Per plane, with u = 2^-24, T = (b - o) * invd the real value, e the exact
-// test's value and c the FMA's: |e - T| <= 2.0001u|T|, |c - T| <= u|T| + 1.0001uM, where
-// M = max_a |o_a * invd_a| (the rounding of the per-lane product), so
-// |c - e| <= 3.001u|c| + 1.001uM. Carried through the max/min chains (lo >= tmin > 0 on a
-// passing exact test) and the reference's tmax * 1.00000024, an exact pass implies
-//     lo_c <= hi_c * (1 + 11.1u) + 2.1uM,
-// which the inner test admits with room: lo_c <= fma(hi_c, 1 + 16u, max(16uM, 2^-100))
-// (the floor covers underflow). The inner test is 12 VALU against the exact test's 18.
-// It is taken only when every live lane has a finite invd and M <= 2^100 (a zero direction
-// component or a huge offset makes the wave use the exact test everywhere), and only for
-// single-octant waves (OCT < 8), on nodes whose four slots are all inner (one scalar branch
-// per node). Compile-time switch YRT_ANY_CONSERVATIVE, off: it loses (DESIGN.md §5 round 5:
-// c4 shadow 11.63 -> 12.49 ms per node, 12.91 with a branch per inner slot -- the walk is
-// co-bound by the scalar unit, which the branches load, and the planes cost 6 VGPRs and 6
-// SGPR spills).
-#ifndef YRT_ANY_CONSERVATIVE
-#define YRT_ANY_CONSERVATIVE 0
-#endif
-struct inner_planes {
-    vec3f noci;  // -(o * invd), per lane
-    float marg;  // max(16uM, 2^-100), per lane
-    bool on;     // wave-uniform: the inner slots use the conservative test
-};
-
-__device__ __forceinline__ inner_planes make_inner_planes(vec3f o, vec3f ci, unsigned long long lanes) {
-    inner_planes p;
-    p.noci = {-(o.x * ci.x), -(o.y * ci.y), -(o.z * ci.z)};
-    const float M = fmaxf(fmaxf(fabsf(p.noci.x), fabsf(p.noci.y)), fabsf(p.noci.z));
-    p.marg = fmaxf(M * 0x1p-20f, 0x1p-100f);
-    // (a NaN fails every comparison: that lane turns the test off for the wave)
-    const bool ok = M <= 0x1p100f && fabsf(ci.x) <= 0x1p100f && fabsf(ci.y) <= 0x1p100f && fabsf(ci.z) <= 0x1p100f;
-    p.on = YRT_ANY_CONSERVATIVE && !(ballot(!ok) & lanes);
-    return p;
-}
-
-template <int OCT>
-__device__ __forceinline__ bool box_oct_inner(const inner_planes& P, vec3f invd, float tmin_r, float tmax_r, float lx,
-                                              float ly, float lz, float hx, float hy, float hz) {
-    const float nx = (OCT & 1) ? hx : lx, fx = (OCT & 1) ? lx : hx;
-    const float ny = (OCT & 2) ? hy : ly, fy = (OCT & 2) ? ly : hy;
-    const float nz = (OCT & 4) ? hz : lz, fz = (OCT & 4) ? lz : hz;
-    const float t0x = fmaf(nx, invd.x, P.noci.x), t0y = fmaf(ny, invd.y, P.noci.y), t0z = fmaf(nz, invd.z, P.noci.z);
-    const float t1x = fmaf(fx, invd.x, P.noci.x), t1y = fmaf(fy, invd.y, P.noci.y), t1z = fmaf(fz, invd.z, P.noci.z);
-    const float lo = fmaxf(fmaxf(fmaxf(t0x, t0y), t0z), tmin_r);
-    const float hi = fminf(fminf(fminf(t1x, t1y), t1z), tmax_r);
-    return lo <= fmaf(hi, 1.00000095367431640625f, P.marg);  // 1 + 2^-20
-}
-
 // the slab tests of a wide step on the record r: m[k] = the lanes of `mask` that pass
 // slot k's box (0 for a slot the node does not have: a scalar branch around it), w[k] =
-// slot k's child word. A node of four inner slots takes box_oct_inner when P.on.
+// slot k's child word.
 template <int OCT>
 __device__ __forceinline__ void wide_tests(const float4 (&r)[7], vec3f co, vec3f ci, float tmin, float tmax,
-                                           const inner_planes& P, unsigned long long mask, uint32_t (&w)[4],
-                                           unsigned long long (&m)[4]) {
+                                           unsigned long long mask, uint32_t (&w)[4], unsigned long long (&m)[4]) {
     const float lx[4] = {r[0].x, r[0].y, r[0].z, r[0].w}, ly[4] = {r[1].x, r[1].y, r[1].z, r[1].w},
                 lz[4] = {r[2].x, r[2].y, r[2].z, r[2].w}, hx[4] = {r[3].x, r[3].y, r[3].z, r[3].w},
                 hy[4] = {r[4].x, r[4].y, r[4].z, r[4].w}, hz[4] = {r[5].x, r[5].y, r[5].z, r[5].w};
     w[0] = (uint32_t)uniform(ibits(r[6].x)), w[1] = (uint32_t)uniform(ibits(r[6].y));
     w[2] = (uint32_t)uniform(ibits(r[6].z)), w[3] = (uint32_t)uniform(ibits(r[6].w));
-    if (YRT_ANY_CONSERVATIVE && OCT < 8 && P.on && !((w[0] | w[1] | w[2] | w[3]) & wide_leaf)) {
-        // a node of four inner slots: all four take the inner test, one branch per node
-#pragma unroll
-        for (int k = 0; k < 4; k++)
-            m[k] = ballot(box_oct_inner<OCT < 8 ? OCT : 0>(P, ci, tmin, tmax, lx[k], ly[k], lz[k], hx[k], hy[k], hz[k])) &
-                   mask;
-        return;
-    }
 #pragma unroll
     for (int k = 0; k < 4; k++) {
         if (k < 2 || w[k] != wide_leaf) {  // every wide node has >= 2 slots but a leaf root's 1
@@ -1195,12 +1094,11 @@ __device__ __forceinline__ void wide_tests(const float4 (&r)[7], vec3f co, vec3f
 // they pop in slot order. Returns true to continue the descent from `cur`.
 template <int OCT>
 __device__ __forceinline__ bool wide_step(const float4 (&r)[7], vec3f co, vec3f ci, float tmin, float tmax,
-                                          const inner_planes& P,
                                           uint32_t& cur, unsigned long long& mask, int& sp, int& stk_word,
                                           int& stk_mlo, int& stk_mhi, int floor, unsigned long long done) {
     uint32_t w[4];
     unsigned long long m[4];
-    wide_tests<OCT>(r, co, ci, tmin, tmax, P, mask, w, m);
+    wide_tests<OCT>(r, co, ci, tmin, tmax, mask, w, m);
     unsigned long long cm = 0;
     uint32_t cw = 0;
     // the select chain as written for the scalar unit. Chain A tests the slots from the
@@ -1333,14 +1231,13 @@ __device__ __forceinline__ bool wide_step(const float4 (&r)[7], vec3f co, vec3f 
 // packet_occluded_wide2)
 template <int OCT, int LDSN, bool ASM = false>
 __device__ __forceinline__ void wide_descend(const f4* base, const float4* lds, vec3f co, vec3f ci,
-                                             const inner_planes& P,
                                              float tmin, float tmax, uint32_t& cur, unsigned long long& mask,
                                              int& sp, int& stk_word, int& stk_mlo, int& stk_mhi, int floor,
                                              unsigned long long done, unsigned& nsteps) {
 #if YRT_WIDE_ASM && !defined(YRT_WIDE_STATS)
     // the same loop as one asm block (wide_asm.h, tools/gen_wide_asm.py) for the records read
     // through the scalar cache and the exact slab tests
-    if constexpr (ASM && LDSN == 0 && OCT < 8 && !YRT_ANY_CONSERVATIVE) {
+    if constexpr (ASM && LDSN == 0 && OCT < 8) {
         auto u64 = [](unsigned long long v) {
             return (unsigned long long)(uint32_t)uniform((int)(v >> 32)) << 32 | (uint32_t)uniform((int)(uint32_t)v);
         };
@@ -1365,11 +1262,11 @@ __device__ __forceinline__ void wide_descend(const f4* base, const float4* lds, 
             const float4* p = lds + (cur >> 4);
 #pragma unroll
             for (int k = 0; k < 7; k++) r[k] = p[k];
-            more = wide_step<OCT>(r, co, ci, tmin, tmax, P, cur, mask, sp, stk_word, stk_mlo, stk_mhi, floor, done);
+            more = wide_step<OCT>(r, co, ci, tmin, tmax, cur, mask, sp, stk_word, stk_mlo, stk_mhi, floor, done);
         } else {
             float4 r[7];
             ld_wide_record(wbase, cur, r);
-            more = wide_step<OCT>(r, co, ci, tmin, tmax, P, cur, mask, sp, stk_word, stk_mlo, stk_mhi, floor, done);
+            more = wide_step<OCT>(r, co, ci, tmin, tmax, cur, mask, sp, stk_word, stk_mlo, stk_mhi, floor, done);
         }
         if (!more) return;
     }
@@ -1425,8 +1322,6 @@ __device__ __forceinline__ bool packet_occluded_wide2(const dev_scene_view& S, c
     vec3f icd, ici;
     enter_direction(frame3f{{1, 0, 0}, {0, 1, 0}, {0, 0, 1}, {0, 0, 0}}, wd, live, icd, ici);
     const int ioct = wave_octant(ici, live);
-    // the inner slots' conservative planes of the current level (recomputed with co / ci)
-    inner_planes ip = make_inner_planes(wo, wi, live);
     unsigned nsteps0 = 0, nsteps1 = 0;
 #ifdef YRT_WIDE_STATS
     unsigned ws[16] = {1, 0, 0, 0, 0, 0, 0, 0};
@@ -1438,7 +1333,7 @@ __device__ __forceinline__ bool packet_occluded_wide2(const dev_scene_view& S, c
             DBG_CHECK(((level == 0 && tbase != S.wnodes) || cur < (uint32_t)S.nwnodes * wide_record_bytes) && sp >= 0 &&
                           sp < 61, 4, (int)cur, sp, level,
                       base, 0);
-#define YRT_WD(o) wide_descend<o, LDSN, ASM>(level ? S.wnodes : tbase, lds, co, ci, ip, tmin, tmax, cur, mask, sp, stk_word, \
+#define YRT_WD(o) wide_descend<o, LDSN, ASM>(level ? S.wnodes : tbase, lds, co, ci, tmin, tmax, cur, mask, sp, stk_word, \
                                          stk_mlo, stk_mhi, wfloor, done, level ? nsteps1 : nsteps0)
             switch (oct) {
                 case 0: YRT_WD(0); break;
@@ -1541,7 +1436,6 @@ __device__ __forceinline__ bool packet_occluded_wide2(const dev_scene_view& S, c
                     WSTAT(3, 1u);
                     WSTAT(12, mask ? 0u : 1u);  // entries whose root box no lane passes
                     oct = ident ? ioct : wave_octant(ci, live & ~done);
-                    ip = make_inner_planes(co, ci, mask);
                     if (mask) break;
                     continue;
                 }
@@ -1550,7 +1444,6 @@ __device__ __forceinline__ bool packet_occluded_wide2(const dev_scene_view& S, c
                 cd = wd;
                 ci = wi;
                 oct = woct;
-                ip = make_inner_planes(wo, wi, live & ~done);
             }
             if (sp == 0) {
                 finished = true;

@@ -367,10 +367,6 @@ __device__ __attribute__((noinline)) float pow_f64_path(float x, float y) {
 }
 __device__ __forceinline__ float powf_cr(float x, float y) {
     if (y == 0.0f) return 1.0f;
-#ifdef YRT_DIAG_POW_F32
-    // diagnostic build only (an A/B of what the f64 path costs): NOT the reference's values
-    return __builtin_amdgcn_exp2f(y * __builtin_amdgcn_logf(x));
-#endif
     // results below 2^-150 round to +0 (the f64 path gives exp2(-inf) = +0 for x = 0).
     // y * log2(x) < -151 by v_log_f32 (error ~2^-23 relative) puts the exact value below
     // -150 with a wide margin.
@@ -429,17 +425,14 @@ struct surface {
     int mcls;  // the material's shadow class (yrt_device.h mat_class_shift)
 };
 
-#ifndef YRT_FAST_NORMALIZE
-#define YRT_FAST_NORMALIZE 1  // shadow-ray setup and shading: normalize / length / ke / r^2 through fast_div.h
-#endif
-
+// shadow-ray setup and shading take normalize / length / ke / r^2 through fast_div.h.
 // normalize(a) and length(a) (yrt_math.h, vmath.h:118-122) with fast_div.h's sqrt_nr and
 // rcp_nr when every active lane's dot(a, a) is in sqrt_nr's range -- then l lies in
 // [2^-48, 2^64), is not 0, and 1/l is normal, where both are bit-identical to sqrtf and
 // 1.0f / l -- else the plain calls. Wave-uniform choice: called in any control flow.
 __device__ __forceinline__ void normalize_len(vec3f a, vec3f& n, float& len) {
     const float d = dot(a, a);
-    if (YRT_FAST_NORMALIZE && !__ballot(!sqrt_nr_ok(d))) {
+    if (!__ballot(!sqrt_nr_ok(d))) {
         len = sqrt_nr(d);
         n = a * rcp_nr(len);
     } else {

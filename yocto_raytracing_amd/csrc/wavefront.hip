@@ -124,7 +124,7 @@ struct wf_buffers {
     int* lcount;            // per (bundle, light): candidate leaves, -1 = walk the tree
     int* lskip;             // per (bundle, light): instances of its listed leaves its hull excludes
     f4* lists;              // per (bundle, light): bundle_recs wide records (wide_record_bytes each)
-    f4* slists;             // per (super-bundle, light): a leaf list (YRT_BUNDLE_SUPER)
+    f4* slists;             // per (super-bundle, light): its bundles' common leaf list (k_bundle_super)
     // camera lists (the closest hit of the camera rays, k_camera_lists)
     int cam_lists;          // 1: this chunk's camera rays walk their tile's list
     int* ccount;            // per 8x8-pixel tile of the chunk: listed leaves, -1 = walk the tree
@@ -259,91 +259,44 @@ __device__ __forceinline__ void flush_work(unsigned long long* counters, const w
 // compiler: its stores would be FLAT, which count against LGKM_CNT as well, so the walk's
 // next s_waitcnt lgkmcnt(0) (every record fetch) would wait for them to reach memory.
 typedef float gvec4 __attribute__((ext_vector_type(4)));
-#ifndef YRT_NT_STREAMS
-// the per-sample workspace streams (surface records, occlusion bytes) are written and read
-// with the non-temporal hint, so that they pass through L2 without evicting the scene
-// (A/B in one process, profiles/r4/ab_nt: c4 24.77 -> 24.62 ms, rank 0 of 8 / 4 and c3
-// -0.6 to -0.8 %, identical images)
-#define YRT_NT_STREAMS 1
-#endif
 // a constant made where it is used: v_mov of the immediate in volatile asm, which the compiler
 // does not hoist out of a persistent kernel's item loop (a hoisted {0, 0, 0, -1} register
 // tuple is held across the walk and spilled: the tuple is not rematerialised)
-#ifndef YRT_R5_VCONST
-#define YRT_R5_VCONST 1
-#endif
 template <int IMM>
 __device__ __forceinline__ float vconst() {
-    if (!YRT_R5_VCONST) return __int_as_float(IMM);
     float r;
     asm volatile("v_mov_b32 %0, %1" : "=v"(r) : "n"(IMM));
     return r;
 }
+// The per-sample workspace streams (surface records, occlusion bytes) are written and read
+// with the non-temporal hint, so that they pass through L2 without evicting the scene
+// (A/B in one process, profiles/r4/ab_nt: c4 24.77 -> 24.62 ms, rank 0 of 8 / 4 and c3
+// -0.6 to -0.8 %, identical images)
 __device__ __forceinline__ void gstore(f4* p, int idx, float x, float y, float z, float w) {
-    auto* q = (__attribute__((address_space(1))) gvec4*)p + idx;
-    if (YRT_NT_STREAMS)
-        __builtin_nontemporal_store(gvec4{x, y, z, w}, q);
-    else
-        *q = gvec4{x, y, z, w};
+    __builtin_nontemporal_store(gvec4{x, y, z, w}, (__attribute__((address_space(1))) gvec4*)p + idx);
 }
 __device__ __forceinline__ void gstore(float* p, int idx, float x) {
-    auto* q = (__attribute__((address_space(1))) float*)p + idx;
-    if (YRT_NT_STREAMS)
-        __builtin_nontemporal_store(x, q);
-    else
-        *q = x;
+    __builtin_nontemporal_store(x, (__attribute__((address_space(1))) float*)p + idx);
 }
-// a workspace stream's record / byte (see YRT_NT_STREAMS)
+// a workspace stream's record / float / byte
 __device__ __forceinline__ float4 ld4s(const f4* p) {
-    if (YRT_NT_STREAMS) {
-        const gvec4 v = __builtin_nontemporal_load((const __attribute__((address_space(1))) gvec4*)p);
-        return make_float4(v.x, v.y, v.z, v.w);
-    }
-    return ld4(p);
+    const gvec4 v = __builtin_nontemporal_load((const __attribute__((address_space(1))) gvec4*)p);
+    return make_float4(v.x, v.y, v.z, v.w);
 }
 __device__ __forceinline__ float lds1(const float* p) {
-    if (YRT_NT_STREAMS) return __builtin_nontemporal_load((const __attribute__((address_space(1))) float*)p);
-    return *p;
+    return __builtin_nontemporal_load((const __attribute__((address_space(1))) float*)p);
 }
 __device__ __forceinline__ unsigned char ldb(const unsigned char* p) {
-    if (YRT_NT_STREAMS) return __builtin_nontemporal_load((const __attribute__((address_space(1))) unsigned char*)p);
-    return *p;
+    return __builtin_nontemporal_load((const __attribute__((address_space(1))) unsigned char*)p);
 }
 __device__ __forceinline__ void stb(unsigned char* p, unsigned char v) {
-    if (YRT_NT_STREAMS)
-        __builtin_nontemporal_store(v, (__attribute__((address_space(1))) unsigned char*)p);
-    else
-        *p = v;
+    __builtin_nontemporal_store(v, (__attribute__((address_space(1))) unsigned char*)p);
 }
 
-#ifndef YRT_SKIP_UNUSED_V
-#define YRT_SKIP_UNUSED_V 1  // a scene without textures neither writes nor reads the surface's v
-#endif
-#ifndef YRT_HIT16
-// 1: the closest-hit kernels write a 16-byte hit record {slot, ei, w1, w2} per sample into
-// surf0 instead of the 36-byte surface {p, mat*4+kind} {n, u} {v}; the shadow setup and
-// k_shade evaluate the surface from it (eval_surface) where they need p, n, uv
-#define YRT_HIT16 0
-#endif
-// the sample's record in surf0: HIT16 {slot (-1 miss, -2 not a sample), ei, w1, w2}, else
-// {p, info (mat*4+kind, -1 miss, -2 not a sample)}; the slot/info field
-__device__ __forceinline__ int sample_state(float4 s0) { return YRT_HIT16 ? ibits(s0.x) : ibits(s0.w); }
+// the sample's record in surf0: {p, info (mat*4+kind, -1 miss, -2 not a sample)}; the info field
+__device__ __forceinline__ int sample_state(float4 s0) { return ibits(s0.w); }
 __device__ __forceinline__ void store_not_sample(const wf_buffers& B, int idx) {
-    if (YRT_HIT16)
-        gstore(B.surf0, idx, __int_as_float(-2), 0, 0, 0);
-    else
-        gstore(B.surf0, idx, vconst<0>(), vconst<0>(), vconst<0>(), vconst<-2>());
-}
-// a HIT16 record's surface (eval_pos/eval_norm/eval_texcoord, scene.h:159-218); ew.x is
-// rebuilt as packet_first builds it (1 - w1 - w2, the same bits)
-__device__ __forceinline__ surface hit16_surface(const dev_scene_view& S, float4 s0) {
-    return eval_surface(S, ibits(s0.x), ibits(s0.y), vec4f{1 - s0.z - s0.w, s0.z, s0.w, 0});
-}
-__device__ __forceinline__ void store_hit16(const wf_buffers& B, int idx, bool hit, const hit_record& hr) {
-    if (!hit)
-        gstore(B.surf0, idx, __int_as_float(-1), 0, 0, 0);
-    else
-        gstore(B.surf0, idx, __int_as_float(hr.slot), __int_as_float(hr.ei), hr.ew.y, hr.ew.z);
+    gstore(B.surf0, idx, vconst<0>(), vconst<0>(), vconst<0>(), vconst<-2>());
 }
 
 // The surface record of a sample: the hit's surface is evaluated and stored on the hit lanes
@@ -366,7 +319,7 @@ __device__ __forceinline__ vec3f store_hit_surface(const dev_scene_view& S, cons
     gstore(B.surf0, idx, sf.p.x, sf.p.y, sf.p.z, __int_as_float(surf_info(sf)));
     gstore(B.surf1, idx, sf.n.x, sf.n.y, sf.n.z, sf.uv.x);
     // uv is read only by texture lookups: a scene without textures never needs it
-    if (!YRT_SKIP_UNUSED_V || B.need_v) gstore(B.surfv, idx, sf.uv.y);
+    if (B.need_v) gstore(B.surfv, idx, sf.uv.y);
     return sf.p;
 }
 
@@ -438,17 +391,13 @@ __device__ __forceinline__ unsigned xcd_runs(unsigned b, unsigned n) {
 // ke / rr (vec3f / float: three divisions) with fast_div.h's div_nr when every active
 // lane's operands are in its range
 __device__ __forceinline__ vec3f div3(vec3f ke, float rr) {
-    if (YRT_FAST_NORMALIZE &&
-        !__ballot(!(div_nr_ok(ke.x, rr) && div_nr_ok(ke.y, rr) && div_nr_ok(ke.z, rr)))) {
+    if (!__ballot(!(div_nr_ok(ke.x, rr) && div_nr_ok(ke.y, rr) && div_nr_ok(ke.z, rr)))) {
         const float y = rcp_nr(rr);
         return {div_nr(ke.x, rr, y), div_nr(ke.y, rr, y), div_nr(ke.z, rr, y)};
     }
     return ke / rr;
 }
 
-#ifndef YRT_SHADOW_CULL
-#define YRT_SHADOW_CULL 1
-#endif
 // ---- shadow rays whose light term is exactly zero are not traced ----
 // shade() (raytrace.cpp:133-183) adds a light's term c += ld + ls only when intersect_any
 // finds no occluder; skipping it and adding it are the same when the term is +-0 in every
@@ -500,13 +449,13 @@ __device__ __forceinline__ ray3 camera_ray_w(const dev_camera& cam, int W, int H
     const float fns = (float)ns, fw = (float)W, fh = (float)H;
     const float a = ii + 0.5f, b = jj + 0.5f;
     float u, v;
-    if (YRT_FAST_NORMALIZE && (in_range || !__ballot(!(div_nr_ok(a, fns) && div_nr_ok(b, fns))))) {
+    if (in_range || !__ballot(!(div_nr_ok(a, fns) && div_nr_ok(b, fns)))) {
         const float y = rcp_nr(fns);
         u = i + div_nr(a, fns, y), v = j + div_nr(b, fns, y);
     } else {
         u = i + a / fns, v = j + b / fns;
     }
-    if (YRT_FAST_NORMALIZE && (in_range || !__ballot(!(div_nr_ok(u, fw) && div_nr_ok(v, fh))))) {
+    if (in_range || !__ballot(!(div_nr_ok(u, fw) && div_nr_ok(v, fh)))) {
         u = div_nr(u, fw, rcp_nr(fw)), v = div_nr(v, fh, rcp_nr(fh));
     } else {
         u = u / fw, v = v / fh;
@@ -538,9 +487,6 @@ __device__ __forceinline__ ray3 camera_ray_w(const dev_camera& cam, int W, int H
 // any-hit answer does not depend on which inner boxes were tested.
 // A bundle whose light is rotated, whose hit points are not finite or whose list would be
 // longer walks the tree.
-#ifndef YRT_SHADOW_BUNDLES
-#define YRT_SHADOW_BUNDLES 1
-#endif
 #ifndef YRT_BUNDLE_ITEMS
 #define YRT_BUNDLE_ITEMS 64  // 64-sample items per bundle (at most 64: one per lane of the list builder)
 #endif
@@ -548,14 +494,6 @@ constexpr int bundle_g = YRT_BUNDLE_ITEMS;
 static_assert(bundle_g >= 1 && bundle_g <= 64, "one item per lane of k_bundle_lists");
 #ifndef YRT_BUNDLE_MIN_TOP
 #define YRT_BUNDLE_MIN_TOP 8  // bundles only when the instance level's wide tree has this many records
-#endif
-#ifndef YRT_BUNDLE_SORT
-// a bundle's leaves in the order its rays meet them: 1 from the hit points towards the light,
-// 2 from the light towards the hit points, 0 in tree order. A/B in one process
-// (profiles/r4/ab_bundle_sort): c4 shadow 11.82 -> 11.72 / 11.62 ms (1 / 2), instance1k
-// 7.42 -> 7.30 / 7.39, instance100k (lists off) unchanged; putting the leaf that holds the
-// hit points' centre (their own instance) last: 11.71 / 7.39
-#define YRT_BUNDLE_SORT 2
 #endif
 #ifndef YRT_LISTS_MIN_SPP
 // the lists' cost is per 8x8-pixel tile (~0.2 ms at 1080p), their gain per sample: in one
@@ -565,17 +503,12 @@ static_assert(bundle_g >= 1 && bundle_g <= 64, "one item per lane of k_bundle_li
 // pixel (a 3x3 grid)
 #define YRT_LISTS_MIN_SPP 9
 #endif
-#ifndef YRT_INSTANCE_MASKS
-// the list builders mark the instances of a listed leaf that their cone / hull excludes, and
-// the walks skip them (k_camera_lists, k_bundle_lists; dev_scene_view ibox)
-#define YRT_INSTANCE_MASKS 1
-#endif
+// (the list builders also mark the instances of a listed leaf that their cone / hull excludes,
+// and the walks skip them: k_camera_lists, k_bundle_lists; dev_scene_view ibox)
 constexpr int bundle_max = 16;        // candidate leaves per list
 constexpr int bundle_recs = 5;        // wide records per list: a chain (3 + 3 + 3 + 3 + 4 leaves)
 constexpr int bundle_max_lights = 8;  // more lights: no bundles (the lists' memory grows with them)
-#ifndef YRT_CAMERA_LISTS
-#define YRT_CAMERA_LISTS 1  // camera rays walk per-tile leaf lists (k_camera_lists, packet_first's list mode)
-#endif
+// camera rays walk per-tile leaf lists (k_camera_lists, packet_first's list mode)
 #ifndef YRT_CAMERA_LIST_MAX
 #define YRT_CAMERA_LIST_MAX 32  // leaves per tile list (more: the tile's rays walk the tree)
 #endif
@@ -646,13 +579,6 @@ __device__ __forceinline__ void store_item_box(const wf_buffers& B, int idx, boo
     }
 }
 
-#ifndef YRT_R5_SURF
-#define YRT_R5_SURF 1
-#endif
-#ifndef YRT_PRIMARY_REL
-#define YRT_PRIMARY_REL 1  // camera rays walk the instance level on camera-relative records
-#endif
-
 // ---- level 0: camera rays + closest hit + surface ----
 // the camera samples idx of one wave: eval_camera, closest hit, surface record
 template <bool COUNT, bool PACKET, typename SE, int BS = packet_block, int LDSN = 0, bool LIST = false>
@@ -716,7 +642,7 @@ __device__ __forceinline__ bool primary_samples(const dev_scene_view& S, const d
     // of the 8x8-pixel tile this wave's samples lie in (a wave straddling two tiles walks
     // the tree)
     bool hit;
-    if constexpr (PACKET && YRT_PRIMARY_REL) {
+    if constexpr (PACKET) {
         const f4* lbase = nullptr;
         int ln = -1;
         if (LIST && !COUNT) {
@@ -746,25 +672,9 @@ __device__ __forceinline__ bool primary_samples(const dev_scene_view& S, const d
     vec3f hp = {0, 0, 0};
     if (valid) {
         if (COUNT && hit) wc.hits++;
-        if (YRT_HIT16) {
-            store_hit16(B, idx, hit, hr);
-            if (YRT_SHADOW_BUNDLES && hit && B.bundles) hp = eval_surface(S, hr.slot, hr.ei, hr.ew).p;
-        } else if (YRT_R5_SURF) {
-            hp = store_hit_surface(S, B, idx, hit, hr);
-        } else {
-            surface sf = {};
-            if (hit) sf = eval_surface(S, hr.slot, hr.ei, hr.ew);
-            if (!hit)
-                gstore(B.surf0, idx, 0, 0, 0, __int_as_float(-1));
-            else {
-                gstore(B.surf0, idx, sf.p.x, sf.p.y, sf.p.z, __int_as_float(surf_info(sf)));
-                gstore(B.surf1, idx, sf.n.x, sf.n.y, sf.n.z, sf.uv.x);
-                if (!YRT_SKIP_UNUSED_V || B.need_v) gstore(B.surfv, idx, sf.uv.y);
-            }
-            hp = sf.p;
-        }
+        hp = store_hit_surface(S, B, idx, hit, hr);
     }
-    if (YRT_SHADOW_BUNDLES && !COUNT && B.bundles) store_item_box(B, idx, valid && hit, hp);
+    if (!COUNT && B.bundles) store_item_box(B, idx, valid && hit, hp);
     return valid;
 }
 
@@ -962,9 +872,6 @@ static_assert((YRT_PRIMARY_WAVES * 4 * 64) % YRT_PRIMARY_SP_BLOCK == 0, "whole b
 // instead: 62 SGPR and 12 VGPR spills, c4 unchanged.)
 #define YRT_PRIMARY_PERSIST_MIN_ITEMS 0
 #endif
-#ifndef YRT_R5_IDXLANE
-#define YRT_R5_IDXLANE 1
-#endif
 #ifndef YRT_PRIMARY_BLOCK_CHUNK
 #define YRT_PRIMARY_BLOCK_CHUNK 16  // (64: the same)
 #endif
@@ -1010,8 +917,9 @@ __global__ __launch_bounds__(YRT_PRIMARY_SP_BLOCK, YRT_PRIMARY_WAVES) void k_pri
         tail_items++;
 #endif
         asm volatile("" ::: "memory");
+        // (lane_now(), not `lane`: a lane index held across the walk would be spilled)
         const bool valid = primary_samples<false, true, SE, SPB, LDSN, LIST>(S, A_lds, C_lds, B_lds, T,
-                                                                            (int)(it * 64) + (YRT_R5_IDXLANE ? lane_now() : (int)lane), wc, lds_rec);
+                                                                            (int)(it * 64) + lane_now(), wc, lds_rec);
         valid_n += (unsigned)__popcll(ballot(valid));
     }
 #ifdef YRT_TAIL_STATS
@@ -1052,12 +960,7 @@ __global__ __launch_bounds__(WF_BLOCK, YRT_TRACE_WAVES) void k_rays_first(dev_sc
     }
     hit_record hr = {-1, -1, {0, 0, 0, 0}, 0};
     const bool hit = T.trace(S, ray, valid, hr, wc);
-    if (valid) {
-        if (YRT_HIT16)
-            store_hit16(B, idx, hit, hr);
-        else
-            store_hit_surface(S, B, idx, hit, hr);
-    }
+    if (valid) store_hit_surface(S, B, idx, hit, hr);
     // one intersect_first and one level-0 shade() call per ray
     flush_block<2>(counters, {cnt_rays, cnt_samples}, {valid ? 1ull : 0ull, valid ? 1ull : 0ull});
 }
@@ -1088,11 +991,7 @@ __global__ __launch_bounds__(WF_BLOCK, YRT_TRACE_WAVES) void k_bounce(dev_scene_
         const bool hit = T.trace(S, ray, valid, hr, wc);
         if (valid) {
             if (COUNT && hit) wc.hits++;
-            if (YRT_HIT16) {
-                store_hit16(B, idx, hit, hr);
-            } else {
-                store_hit_surface(S, B, idx, hit, hr);
-            }
+            store_hit_surface(S, B, idx, hit, hr);
         }
     }
     }
@@ -1136,7 +1035,7 @@ __global__ __launch_bounds__(shadow_block<PACKET>(), YRT_SHADOW_WAVES) void k_sh
         float r = 1.0f;
         float4 s1 = {0, 0, 0, 0}, ro4 = make_float4(cam_o.x, cam_o.y, cam_o.z, 0.0f);
         ray3 sr = {{0, 0, 0}, {0, 0, 1}, 0.01f, 1.0f};
-        constexpr bool CULL = YRT_SHADOW_CULL && !COUNT && !YRT_HIT16;
+        constexpr bool CULL = !COUNT;  // (the instrumented pass traces every ray)
         if (j < n) {
             float4 s0 = ld4s(B.surf0 + idx);
             if (CULL) {  // n and the view point, for light_term_zero
@@ -1145,7 +1044,7 @@ __global__ __launch_bounds__(shadow_block<PACKET>(), YRT_SHADOW_WAVES) void k_sh
             }
             info = sample_state(s0);
             if (info >= 0) {
-                const vec3f p = YRT_HIT16 ? hit16_surface(S, s0).p : xyz(s0);
+                const vec3f p = xyz(s0);
                 vec3f tp = transform_point(lf, lp0 - p);
                 vec3f l;
                 normalize_len(tp, l, r);
@@ -1209,16 +1108,13 @@ __global__ __launch_bounds__(shadow_block<PACKET>(), YRT_SHADOW_WAVES) void k_ra
     float4 s1 = {0, 0, 0, 0};
     vec3f ro = {0, 0, 0};
     ray3 sr = {{0, 0, 0}, {0, 0, 1}, 0.01f, 1.0f};
-    constexpr bool CULL = YRT_SHADOW_CULL && !YRT_HIT16;
     if (idx < nsamp) {
         float4 s0 = ld4s(B.surf0 + idx);
-        if (CULL) {  // n and the view point, for light_term_zero
-            s1 = ld4s(B.surf1 + idx);
-            ro = ray_origin(B, idx);
-        }
+        s1 = ld4s(B.surf1 + idx);  // n and the view point, for light_term_zero
+        ro = ray_origin(B, idx);
         info = sample_state(s0);
         if (info >= 0) {
-            const vec3f p = YRT_HIT16 ? hit16_surface(S, s0).p : xyz(s0);
+            const vec3f p = xyz(s0);
             vec3f tp = transform_point(lf, lp0 - p);
             vec3f l;
             normalize_len(tp, l, r);
@@ -1227,12 +1123,11 @@ __global__ __launch_bounds__(shadow_block<PACKET>(), YRT_SHADOW_WAVES) void k_ra
             rays++;
         }
     }
-    if (CULL) {  // (uniform control flow; a lane that is not a hit has info < 0)
-        if (light_term_zero(info, xyz(s1), sr.o, ro, sr.d, r, ke)) {
-            stb(B.occl + (size_t)li * B.capacity + idx, 1);
-            valid = false;
-            culled++;
-        }
+    // (uniform control flow; a lane that is not a hit has info < 0)
+    if (light_term_zero(info, xyz(s1), sr.o, ro, sr.d, r, ke)) {
+        stb(B.occl + (size_t)li * B.capacity + idx, 1);
+        valid = false;
+        culled++;
     }
     hit_record hr;
     bool occ;
@@ -1408,22 +1303,26 @@ static __device__ unsigned long long g_list_time[3][65536][4];
 #define YRT_LT_WRITE(k, i, a, b, c, d)
 #endif
 
-#ifndef YRT_BUNDLE_SUPER
-// two-level build: one tree walk per (super-bundle of 4 consecutive bundles, light) into a
-// list of up to super_max leaves, which each bundle then filters with its own planes
-// instead of walking the tree (a super list that overflows: the bundles walk). A/B in one
-// process (profiles/r4/ab_bundle_super): the lists phase at c4 0.28 -> 0.24 ms, c5 rank 0
+// Two-level build: one tree walk per (super-bundle of 4 consecutive bundles, light) into a
+// list of up to super_max leaves (k_bundle_super), which each bundle then filters with its own
+// planes instead of walking the tree (a super list that overflows: the bundles walk). A/B in
+// one process (profiles/r4/ab_bundle_super): the lists phase at c4 0.28 -> 0.24 ms, c5 rank 0
 // of 8 0.82 -> 0.67 ms; identical images
-#define YRT_BUNDLE_SUPER 1
-#endif
 #ifndef YRT_BUNDLE_FUSED
 // the super lists and the bundle lists in one launch (k_bundle_lists<true>). A/B in one process
 // (profiles/r6/ab/r6e_*): lists phase c4 0.31 -> 0.37 ms, instance100k 0.47 -> 0.60, c5 rank 0
 // of 8 0.82 -> 1.00, rank 0 of 8 0.10 -> 0.09; the block's four waves wait at its barrier for
 // the longest root slot's walk. Off.
+// (Kept although nothing launches it: run() names k_bundle_lists<true> in a plain `if`, so the
+// default build still instantiates it, and with that second caller of hull_walk<super_max>
+// passing a variable only_slot the compiler peels the walk's first iteration in k_bundle_super
+// too. Without the instantiation k_bundle_super comes out as another kernel, 890 instructions
+// for 1147; no other kernel changes. Taking the switch out is a change of a timed kernel, to
+// be measured on its own.)
 #define YRT_BUNDLE_FUSED 0
 #endif
 constexpr int super_bundles = 4;
+static_assert(bundle_g * super_bundles <= 4 * 64, "bundle_box: up to four items per lane");
 constexpr int super_max = 32;
 constexpr int super_list_f4 = 1 + 2 * super_max;  // {count} then {lo, word} {hi, 0} per leaf
 
@@ -1468,7 +1367,7 @@ __global__ __launch_bounds__(256) void k_bundle_super(dev_scene_view S, wf_buffe
 }
 
 // one wave per (bundle, light): the candidate list (see above) -- from the super-bundle's
-// list (YRT_BUNDLE_SUPER) or a walk of the tree -- as a chain of wide records.
+// list, or a walk of the tree where that list overflowed -- as a chain of wide records.
 // FUSED (YRT_BUNDLE_FUSED): one block per (super-bundle, light), wave w its bundle w, and the
 // super-bundle's list is built in the same launch: the four waves write their bundles' boxes to
 // LDS, each walks one root slot's subtree with the super-bundle's hull (the union box), and the
@@ -1550,7 +1449,7 @@ __global__ __launch_bounds__(256) void k_bundle_lists(dev_scene_view S, wf_buffe
     const hull_t H = make_hull(plx, ply, plz, phx, phy, phz, Lp, lane);
     int nc = 0;
     bool overflow = false;
-    if (!FUSED && YRT_BUNDLE_SUPER && bundle_g * super_bundles <= 256) {
+    if (!FUSED) {
         sup = B.slists + (size_t)((g / super_bundles) * nl + li) * super_list_f4;
         sc = __builtin_amdgcn_readfirstlane(__float_as_int(ld4(sup).x));
     }
@@ -1595,19 +1494,21 @@ __global__ __launch_bounds__(256) void k_bundle_lists(dev_scene_view S, wf_buffe
     }
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // the candidate stores, before any lane reads them
     YRT_LT_STAMP(lt1);
-    if (YRT_BUNDLE_SORT && nc > 1) {
-        // the leaves in the order the bundle's rays meet them (box centres projected on the
-        // direction from the hit points to the light; YRT_BUNDLE_SORT), so that the chain's
-        // later records are compact boxes the rays can pass by and an occluded bundle meets
-        // its occluder sooner. The any-hit answer does not depend on the order.
+    if (nc > 1) {
+        // the leaves in the order the bundle's rays meet them, from the light towards the hit
+        // points (box centres projected on that direction), so that the chain's later records
+        // are compact boxes the rays can pass by and an occluded bundle meets its occluder
+        // sooner. The any-hit answer does not depend on the order. A/B in one process
+        // (profiles/r4/ab_bundle_sort), tree order -> from the hit points / from the light: c4
+        // shadow 11.82 -> 11.72 / 11.62 ms, instance1k 7.42 -> 7.30 / 7.39, instance100k (lists
+        // off) unchanged; the leaf that holds the hit points' centre last: 11.71 / 7.39
         const float cx = 0.5f * (plx + phx), cy = 0.5f * (ply + phy), cz = 0.5f * (plz + phz);
         const float dx = Lp.x - cx, dy = Lp.y - cy, dz = Lp.z - cz;
         float e[7] = {};
         float key = INFINITY;
         if (lane < nc) {
             for (int q = 0; q < 7; q++) e[q] = cand[w][lane][q];
-            key = (0.5f * (e[0] + e[3]) - cx) * dx + (0.5f * (e[1] + e[4]) - cy) * dy + (0.5f * (e[2] + e[5]) - cz) * dz;
-            if (YRT_BUNDLE_SORT == 2) key = -key;
+            key = -((0.5f * (e[0] + e[3]) - cx) * dx + (0.5f * (e[1] + e[4]) - cy) * dy + (0.5f * (e[2] + e[5]) - cz) * dz);
             if (!(key == key)) key = INFINITY;  // (a NaN bound: last)
         }
         int rank = 0;  // a permutation of 0 .. nc - 1: ties go by index
@@ -1625,7 +1526,7 @@ __global__ __launch_bounds__(256) void k_bundle_lists(dev_scene_view S, wf_buffe
     // root box test in the instance's space, so the walk skips them (skip bits in the leaf's
     // word: the bundle records' format, bundle_leaf_word)
     int nskip = 0;  // (wave-uniform) instances the hull excludes, over the listed leaves
-    if (YRT_INSTANCE_MASKS && S.inst_masks) {
+    if (S.inst_masks) {
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         for (int e = 0; e < nc; e++) {
             const uint32_t wu = (uint32_t)__builtin_amdgcn_readfirstlane(__float_as_int(cand[w][e][6]));
@@ -1877,7 +1778,7 @@ __global__ __launch_bounds__(256) void k_camera_lists(dev_scene_view S, dev_rend
         // entry's count word, which packet_first's list mode honours (a tree leaf's are 0)
         const uint32_t cw = ubits(hi.w);
         const int count = (int)(cw & 0xffffu);
-        if (YRT_INSTANCE_MASKS && S.ibox && (cw & leaf_bit) && count > 1 && count <= 15) {
+        if (S.ibox && (cw & leaf_bit) && count > 1 && count <= 15) {
             const int first = ibits(lo.w);
             uint32_t skip = 0;
             for (int i = 0; i < count; i++) {
@@ -1973,12 +1874,12 @@ __global__ __launch_bounds__(256) void k_list_stats(wf_buffers B, int ntiles, in
 #define YRT_SHADOW_LDS_RECORDS 85
 #endif
 
-// one light of a 64-sample item of k_shadow_shade_persist: the shadow ray of lane's sample
-// idx = bx * 64 + lane towards light li, and whether it is occluded (a culled ray counts as
-// occluded). valid: the lane has a ray. This is k_shadow_persist's light loop body as a
-// function; k_shadow_persist keeps its own text: its kept variants (YRT_HIT16=1,
-// YRT_SHADOW_CULL=0) do not compile through the function ("invalid operand" in the walk's asm).
-// WCULL: `culled` counts the wave's culled rays (wave-uniform) instead of the lane's
+// one light of a 64-sample item of the persistent any-hit grids (k_shadow_persist and
+// k_shadow_shade_persist): the shadow ray of lane's sample idx = bx * 64 + lane towards light
+// li, and whether it is occluded (a culled ray counts as occluded). valid: the lane has a ray.
+// IL: the item holds every light (its surface loads are the cached ones)
+// WCULL: `culled_n` counts the wave's culled rays (wave-uniform) instead of the lane's
+// carry: where this lane's {l, r} goes for the item's shading, or null
 template <int LDSN, bool IL, bool WCULL = false>
 __device__ __forceinline__ bool shadow_item_light(const dev_scene_view& S, const wf_buffers& B, int nsamp, int bx,
                                                   int li, int nl, unsigned lane, const vec3f& cam_o,
@@ -1999,10 +1900,10 @@ __device__ __forceinline__ bool shadow_item_light(const dev_scene_view& S, const
         // (every light of the item reads the sample's surface again: cached loads, not the
         // streaming ones; holding it across the walks instead spills 5 VGPRs: +0.5 %)
         float4 s0 = IL ? ld4(B.surf0 + idx) : ld4s(B.surf0 + idx);
-        if (YRT_SHADOW_CULL && !YRT_HIT16) s1 = IL ? ld4(B.surf1 + idx) : ld4s(B.surf1 + idx);  // n, for light_term_zero
+        s1 = IL ? ld4(B.surf1 + idx) : ld4s(B.surf1 + idx);  // n, for light_term_zero
         info = sample_state(s0);
         if (info >= 0) {
-            const vec3f p = YRT_HIT16 ? hit16_surface(S, s0).p : xyz(s0);
+            const vec3f p = xyz(s0);
             vec3f tp = transform_point(lf, lp0 - p);
             vec3f l;
             normalize_len(tp, l, r);
@@ -2018,13 +1919,12 @@ __device__ __forceinline__ bool shadow_item_light(const dev_scene_view& S, const
     // not a hit, info < 0, so it implies valid) start the walk as done -- recorded as
     // occluded -- and a wave whose every ray is culled skips it. (Taking them out of `valid`
     // instead trips the compiler inside this loop: "illegal VGPR to SGPR copy".)
-    const bool zero_term =
-        YRT_SHADOW_CULL && !YRT_HIT16 && light_term_zero(info, xyz(s1), sr.o, cam_o, sr.d, r, xyz(lrec[5]));
+    const bool zero_term = light_term_zero(info, xyz(s1), sr.o, cam_o, sr.d, r, xyz(lrec[5]));
     const unsigned long long culled = ballot(zero_term);
     culled_n += WCULL ? (unsigned)__popcll(culled) : zero_term ? 1u : 0u;
-    const bool all_culled = YRT_SHADOW_CULL && !YRT_HIT16 && culled == ballot(valid);
+    const bool all_culled = culled == ballot(valid);
     int lc = -1;  // the bundle's list: its leaf count, -1 = walk the tree
-    if (YRT_SHADOW_BUNDLES && LDSN == 0 && B.bundles) {
+    if (LDSN == 0 && B.bundles) {
         const int gl = (bx / bundle_g) * nl + li;
         lc = __builtin_amdgcn_readfirstlane(B.lcount[gl]);
     }
@@ -2085,62 +1985,14 @@ __global__ __launch_bounds__(SP_BLOCK, YRT_SHADOW_WAVES) void k_shadow_persist(d
 #endif
         const int bx = IL ? (int)it : (int)(it / (unsigned)nl);
         for (int lq = 0; lq < (IL ? nl : 1); lq++) {
-        const int li = IL ? lq : (int)(it % (unsigned)nl);
-        // the light's frame and position: one wave-uniform record, through the scalar cache
-        float4 lrec[6];
-        ld_records_at<6>(S.lights, (unsigned)(6 * li), lrec);
-        const frame3f lf = {xyz(lrec[0]), xyz(lrec[1]), xyz(lrec[2]), xyz(lrec[3])};
-        const vec3f lp0 = xyz(lrec[4]);
-        const int idx = bx * 64 + (int)lane;
-        bool valid = false;
-        int info = -1;
-        float r = 1.0f;
-        float4 s1 = {0, 0, 0, 0};
-        ray3 sr = {{0, 0, 0}, {0, 0, 1}, 0.01f, 1.0f};
-        if (idx < nsamp) {
-            // (every light of the item reads the sample's surface again: cached loads, not the
-            // streaming ones; holding it across the walks instead spills 5 VGPRs: +0.5 %)
-            float4 s0 = IL ? ld4(B.surf0 + idx) : ld4s(B.surf0 + idx);
-            if (YRT_SHADOW_CULL && !YRT_HIT16) s1 = IL ? ld4(B.surf1 + idx) : ld4s(B.surf1 + idx);  // n, for light_term_zero
-            info = sample_state(s0);
-            if (info >= 0) {
-                const vec3f p = YRT_HIT16 ? hit16_surface(S, s0).p : xyz(s0);
-                vec3f tp = transform_point(lf, lp0 - p);
-                vec3f l;
-                normalize_len(tp, l, r);
-                sr = {p, l, 0.01f, r - 0.01f};
-                valid = true;
-            }
-        }
-        rays += (unsigned)__popcll(ballot(valid));
-        // the rays whose light term is zero (light_term_zero, called by every lane in uniform
-        // control flow: its loads and ballots see the whole wave; it is false on a lane that is
-        // not a hit, info < 0, so it implies valid) start the walk as done -- recorded as
-        // occluded -- and a wave whose every ray is culled skips it. (Taking them out of `valid`
-        // instead trips the compiler inside this loop: "illegal VGPR to SGPR copy".)
-        const bool zero_term =
-            YRT_SHADOW_CULL && !YRT_HIT16 && light_term_zero(info, xyz(s1), sr.o, cam_o, sr.d, r, xyz(lrec[5]));
-        const unsigned long long culled = ballot(zero_term);
-        culled_l += zero_term ? 1u : 0u;
-        const bool all_culled = YRT_SHADOW_CULL && !YRT_HIT16 && culled == ballot(valid);
-        bool occ;
-        int lc = -1;  // the bundle's list: its leaf count, -1 = walk the tree
-        if (YRT_SHADOW_BUNDLES && LDSN == 0 && B.bundles) {
-            const int gl = (bx / bundle_g) * nl + li;
-            lc = __builtin_amdgcn_readfirstlane(B.lcount[gl]);
-        }
-        const f4* tbase = S.wnodes;
-        uint32_t troot = (uint32_t)S.wtop_root;
-        if (lc > 0) {  // (the host turns bundles off with LDS-staged records: LDSN == 0 here)
-            tbase = B.lists;
-            troot = (uint32_t)(((bx / bundle_g) * nl + li) * bundle_recs * wide_record_bytes);
-        }
-        // lc == 0: no leaf can be passed by these rays, none is occluded; all_culled: recorded
-        // as occluded, k_shade skips the light
-        occ = all_culled ? true
-                         : lc == 0 ? ((culled >> lane) & 1ull) != 0
-                                   : packet_occluded_wide2<LDSN, true>(S, sr, valid, lds_nodes, tbase, troot, culled);
-        if (valid) stb(B.occl + (size_t)li * B.capacity + idx, occ ? 1 : 0);
+            const int li = IL ? lq : (int)(it % (unsigned)nl);
+            bool valid;  // (idx < nsamp on a valid lane)
+            const bool occ =
+                shadow_item_light<LDSN, IL>(S, B, nsamp, bx, li, nl, lane, cam_o, lds_nodes, rays, culled_l, valid);
+            // (the byte's address in this form, idx an int of its own: with bx * 64 + lane written
+            // into the sum the kernel spills 2 VGPRs)
+            const int idx = bx * 64 + (int)lane;
+            if (valid) stb(B.occl + (size_t)li * B.capacity + idx, occ ? 1 : 0);
         }
     }
 #ifdef YRT_TAIL_STATS
@@ -2159,18 +2011,6 @@ __global__ __launch_bounds__(SP_BLOCK, YRT_SHADOW_WAVES) void k_shadow_persist(d
 #endif
 // OCC4 (scenes with at most four lights): the occlusion bytes are loaded together with the
 // surface, one memory round trip instead of one per light inside the light loop.
-#ifndef YRT_SHADE_LDS_SRGB
-// textured scenes: the srgb table (1 KiB) is copied into LDS per block, so the last
-// link of a texture lookup's chain of dependent loads (material -> texel -> table) is
-// an LDS read
-#define YRT_SHADE_LDS_SRGB 1
-#endif
-#ifndef YRT_FOLD_PREFETCH
-// mirror levels: the parent's fold records (D, la and its material's kr) are loaded at the
-// top of k_shade, beside the sample's own surface, instead of after the shading, so their
-// latency overlaps the light loop rather than following it
-#define YRT_FOLD_PREFETCH 0
-#endif
 #ifndef YRT_SHADE_LEVEL_WAVES
 // the same for the unfused k_shade (reflective scenes: per-level shading, mirror-ray
 // compaction, the fold). Its waits are dependent loads (SQ_WAIT_ANY 76 % at 7 waves); more
@@ -2211,12 +2051,10 @@ __device__ __forceinline__ void shade_hit(const dev_scene_view& S, const wf_buff
     vec3f nrm;
     vec2f uv;
     int mat, kind;
-    if (YRT_HIT16) {
-        const surface sf = hit16_surface(S, s0);
-        p = sf.p, nrm = sf.n, uv = sf.uv, mat = sf.mat, kind = sf.kind;
-    } else {
+    {
         const float4 s1 = ld4s(B.surf1 + idx);
-        p = xyz(s0), nrm = xyz(s1), uv = {s1.w, (!YRT_SKIP_UNUSED_V || B.need_v) ? lds1(B.surfv + idx) : 0.0f};
+        // (v is read only by texture lookups: a scene without textures neither writes nor reads it)
+        p = xyz(s0), nrm = xyz(s1), uv = {s1.w, B.need_v ? lds1(B.surfv + idx) : 0.0f};
         mat = info_mat(info), kind = info & 3;
     }
     const vec3f ro = xyz(ro4);
@@ -2353,17 +2191,19 @@ __device__ __forceinline__ void sum_pixels(const dev_render_args& A, const chunk
     }
 }
 
-// the table a texture lookup ends in (YRT_SHADE_LDS_SRGB: the block's LDS copy, staged here by
-// its BS threads). A scene without textures never looks the table up: it is not staged.
+// the table a texture lookup ends in: the block's LDS copy of the srgb table (1 KiB), staged
+// here by its BS threads, so that the last link of a lookup's chain of dependent loads
+// (material -> texel -> table) is an LDS read. A scene without textures never looks the table
+// up: it is not staged.
 // BARRIER: the copy is followed by its barrier here; otherwise by one of the caller's
-using srgb_table = float[YRT_SHADE_LDS_SRGB ? 256 : 1];
+using srgb_table = float[256];
 template <int BS, bool BARRIER>
 __device__ __forceinline__ const float* stage_srgb(const dev_scene_view& S, srgb_table& srgb_lds) {
-    if (YRT_SHADE_LDS_SRGB && S.ntextures > 0) {  // uniform over the grid
+    if (S.ntextures > 0) {  // uniform over the grid
         for (int q = (int)threadIdx.x; q < 256; q += BS) srgb_lds[q] = S.srgb[q];
         if (BARRIER) __syncthreads();
     }
-    return YRT_SHADE_LDS_SRGB ? srgb_lds : S.srgb;
+    return srgb_lds;
 }
 
 // ---- shading passes (yrt_render_passes): the beauty split into the terms shade() adds up ----
@@ -2433,20 +2273,13 @@ __device__ __forceinline__ void shade_samples(dev_scene_view S, dev_render_args 
             const int info = sample_state(s0);
             vec3f R = {0, 0, 0};
             bool write_r = info != -2;
-            // level >= 1: this sample's ray record {origin, parent index}; with
-            // YRT_FOLD_PREFETCH the parent's fold records are requested now
+            // level >= 1: this sample's ray record {origin, parent index}
             float4 ro4 = (!FUSE && level) ? ld4(B.ray_o(level) + idx) : make_float4(cam_o.x, cam_o.y, cam_o.z, 0.0f);
             if constexpr (RAYS && !FUSE) {
                 if (!level) {
                     const vec3f o = ray_origin(B, idx);
                     ro4 = make_float4(o.x, o.y, o.z, 0.0f);
                 }
-            }
-            float4 pd = {0, 0, 0, 0}, pla = {0, 0, 0, 0}, pkr = {0, 0, 0, 0};
-            if (YRT_FOLD_PREFETCH && !FUSE && level) {
-                const int parent = ibits(ro4.w);
-                pd = ld4(B.rec0(level - 1) + parent), pla = ld4(B.rec1(level - 1) + parent);
-                pkr = ld4(S.mats + 4 * ibits(pd.w) + 2);
             }
             // this sample's pass values (level 0): a miss keeps +0 in each. (Without PASSES an
             // empty object and a null pointer: with its address k_shade came out differently)
@@ -2479,11 +2312,10 @@ __device__ __forceinline__ void shade_samples(dev_scene_view S, dev_render_args 
                 vec3f col = R;
                 int lev = level, node = idx;
                 while (lev > 0) {
-                    const bool pre = YRT_FOLD_PREFETCH && lev == level;
-                    const int parent = pre ? ibits(ro4.w) : ibits(B.ray_o(lev)[node].w);
-                    const float4 d = pre ? pd : ld4(B.rec0(lev - 1) + parent);
-                    const float4 la = pre ? pla : ld4(B.rec1(lev - 1) + parent);
-                    const float4 kr = pre ? pkr : ld4(S.mats + 4 * ibits(d.w) + 2);  // the parent's material kr
+                    const int parent = ibits(B.ray_o(lev)[node].w);
+                    const float4 d = ld4(B.rec0(lev - 1) + parent);
+                    const float4 la = ld4(B.rec1(lev - 1) + parent);
+                    const float4 kr = ld4(S.mats + 4 * ibits(d.w) + 2);  // the parent's material kr
                     vec3f cc = {d.x, d.y, d.z};
                     const vec3f t = {col.x * kr.x, col.y * kr.y, col.z * kr.z};
                     if constexpr (PASSES) {  // the last step, into the camera sample, adds its reflection value
@@ -2582,9 +2414,9 @@ __global__ __launch_bounds__(SB, FUSE ? shade_pass_waves : YRT_SHADE_LEVEL_WAVES
     // rows are one float apart in the banks, so the 18 chains of a pixel read 18 banks
     constexpr int ROW = SB + 1;
     __shared__ float fused[FUSE ? pass_planes * 3 * ROW : 1];
-    __shared__ float srgb_lds[YRT_SHADE_LDS_SRGB ? 256 : 1];
-    const float* lut = YRT_SHADE_LDS_SRGB ? srgb_lds : S.srgb;
-    if (YRT_SHADE_LDS_SRGB && S.ntextures > 0) {  // uniform over the grid
+    __shared__ float srgb_lds[256];
+    const float* lut = srgb_lds;
+    if (S.ntextures > 0) {  // uniform over the grid
         for (int q = (int)threadIdx.x; q < 256; q += SB) srgb_lds[q] = S.srgb[q];
         __syncthreads();
     }
@@ -2619,12 +2451,9 @@ __global__ __launch_bounds__(SB, FUSE ? shade_pass_waves : YRT_SHADE_LEVEL_WAVES
                 vec3f nrm;
                 vec2f uv;
                 int mat, kind;
-                if (YRT_HIT16) {
-                    const surface sf = hit16_surface(S, s0);
-                    p = sf.p, nrm = sf.n, uv = sf.uv, mat = sf.mat, kind = sf.kind;
-                } else {
+                {
                     const float4 s1 = ld4s(B.surf1 + idx);
-                    p = xyz(s0), nrm = xyz(s1), uv = {s1.w, (!YRT_SKIP_UNUSED_V || B.need_v) ? lds1(B.surfv + idx) : 0.0f};
+                    p = xyz(s0), nrm = xyz(s1), uv = {s1.w, B.need_v ? lds1(B.surfv + idx) : 0.0f};
                     mat = info_mat(info), kind = info & 3;
                 }
                 const vec3f ro = xyz(ro4);
@@ -2745,13 +2574,9 @@ __global__ __launch_bounds__(SB, FUSE ? shade_pass_waves : YRT_SHADE_LEVEL_WAVES
 // 4.89 -> 4.60, rank 0 of 8 1.28 -> 1.23; with the 64-spp sum not unrolled c4 was 9.31)
 #define YRT_SHADOW_SHADE_FUSE 1
 #endif
-// (built with the item-lights grid, the cull and the default surface rows: the kept variants
-// without them -- YRT_SHADOW_ITEM_LIGHTS=0, YRT_SHADOW_CULL=0, YRT_HIT16=1 -- keep the two kernels)
-#if (YRT_SHADOW_SHADE_FUSE && YRT_SHADOW_ITEM_LIGHTS && YRT_SHADOW_CULL && !YRT_HIT16)
-#define YRT_SHADOW_SHADE_KERNEL 1
-#else
-#define YRT_SHADOW_SHADE_KERNEL 0
-#endif
+// (built on the item-lights grid: the variant without it, YRT_SHADOW_ITEM_LIGHTS=0, keeps the
+// two kernels)
+#define YRT_SHADOW_SHADE_KERNEL (YRT_SHADOW_SHADE_FUSE && YRT_SHADOW_ITEM_LIGHTS)
 #if !defined(YRT_LIGHT_CARRY)
 // k_shadow_shade_persist: each of an item's first four lights leaves its {l, r} per lane in LDS for
 // the item's shading, which then does not redo transform_point + normalize_len per unoccluded
@@ -2952,16 +2777,11 @@ size_t workspace_bytes(int cap, int spp, int nlights, int nlevels, int pass_plan
     size_t b = align_up(count_bytes(nlevels)) + align_up(32 * sizeof(unsigned)) +
                align_up(list_sums * sizeof(unsigned long long));
     b += align_up(16 * c) * 2 + align_up(4 * c) + align_up(c * std::max(nlights, 1)) + align_up(16 * c);
-    if (YRT_SHADOW_BUNDLES) {
-        const size_t gl = bundle_count(cap) * bundle_lights(nlights);
-        b += align_up(32 * bundle_items(cap)) + 2 * align_up(4 * gl) +
-             align_up((size_t)bundle_recs * wide_record_bytes * gl);
-        if (YRT_BUNDLE_SUPER) b += align_up(super_count(cap) * bundle_lights(nlights) * super_list_f4 * 16);
-    }
-    if (YRT_CAMERA_LISTS) {
-        const size_t nt = camera_tiles(cap, spp);
-        b += 2 * align_up(4 * nt) + align_up(nt * camera_list_max * 32);
-    }
+    const size_t gl = bundle_count(cap) * bundle_lights(nlights);
+    b += align_up(32 * bundle_items(cap)) + 2 * align_up(4 * gl) + align_up((size_t)bundle_recs * wide_record_bytes * gl);
+    b += align_up(super_count(cap) * bundle_lights(nlights) * super_list_f4 * 16);
+    const size_t nt = camera_tiles(cap, spp);
+    b += 2 * align_up(4 * nt) + align_up(nt * camera_list_max * 32);
     // levels >= 1: ray_o, ray_d; levels < last: rec0, rec1 (one slab each)
     if (nlevels > 1) b += 4 * align_up((size_t)(nlevels - 1) * 16 * c);
     return b;
@@ -2984,20 +2804,16 @@ wf_buffers carve(void* base, int cap, int spp, int nlights, int nlevels) {
     B.surfv = (float*)take(4 * c);
     B.occl = (unsigned char*)take(c * std::max(nlights, 1));
     B.rad = (f4*)take(16 * c);
-    if (YRT_SHADOW_BUNDLES) {
-        const size_t gl = bundle_count(cap) * bundle_lights(nlights);
-        B.pbox = (f4*)take(32 * bundle_items(cap));
-        B.lcount = (int*)take(4 * gl);
-        B.lskip = (int*)take(4 * gl);
-        B.lists = (f4*)take((size_t)bundle_recs * wide_record_bytes * gl);
-        if (YRT_BUNDLE_SUPER) B.slists = (f4*)take(super_count(cap) * bundle_lights(nlights) * super_list_f4 * 16);
-    }
-    if (YRT_CAMERA_LISTS) {
-        const size_t nt = camera_tiles(cap, spp);
-        B.ccount = (int*)take(4 * nt);
-        B.cskip = (int*)take(4 * nt);
-        B.clist = (f4*)take(nt * camera_list_max * 32);
-    }
+    const size_t gl = bundle_count(cap) * bundle_lights(nlights);
+    B.pbox = (f4*)take(32 * bundle_items(cap));
+    B.lcount = (int*)take(4 * gl);
+    B.lskip = (int*)take(4 * gl);
+    B.lists = (f4*)take((size_t)bundle_recs * wide_record_bytes * gl);
+    B.slists = (f4*)take(super_count(cap) * bundle_lights(nlights) * super_list_f4 * 16);
+    const size_t nt = camera_tiles(cap, spp);
+    B.ccount = (int*)take(4 * nt);
+    B.cskip = (int*)take(4 * nt);
+    B.clist = (f4*)take(nt * camera_list_max * 32);
     if (nlevels > 1) {
         const size_t slab = (size_t)(nlevels - 1) * 16 * c;
         B.ray_o_ = (f4*)take(slab);
@@ -3191,11 +3007,10 @@ hipError_t run(device_scene& ds, const dev_render_args& A, float4* out, unsigned
         const bool shadow_shade = YRT_SHADOW_SHADE_KERNEL && shadow_persist && !stage &&
                                   nlevels == 1 && !passes && 64 % spp == 0 && ds.nlights <= 32;
         // ... and walk the bundles' candidate lists (k_bundle_lists) instead of the tree
-        const bool bundles_possible = YRT_SHADOW_BUNDLES && !stage && shadow_persist &&
-                                      bundle_lights(ds.nlights) > 0 && ds.view.nwtop >= YRT_BUNDLE_MIN_TOP;
+        const bool bundles_possible = !stage && shadow_persist && bundle_lights(ds.nlights) > 0 &&
+                                      ds.view.nwtop >= YRT_BUNDLE_MIN_TOP;
         // the camera rays walk their tiles' leaf lists (k_camera_lists)
-        const bool cam_lists_possible = YRT_CAMERA_LISTS && YRT_PRIMARY_REL && !stage && !COUNT && PACKET && ds.wide_ok &&
-                                        ds.view.nwtop >= YRT_BUNDLE_MIN_TOP;
+        const bool cam_lists_possible = !stage && !COUNT && PACKET && ds.wide_ok && ds.view.nwtop >= YRT_BUNDLE_MIN_TOP;
         // YRT_LISTS_ON: whenever the scene allows; YRT_LISTS_AUTO: the same from
         // YRT_LISTS_MIN_SPP samples per pixel; _OFF: never (yrt_scene_set_tile_lists)
         const bool lists = ds.lists_mode == 1 || (ds.lists_mode == 0 && spp >= YRT_LISTS_MIN_SPP);
@@ -3223,7 +3038,7 @@ hipError_t run(device_scene& ds, const dev_render_args& A, float4* out, unsigned
                 if (B.cam_lists)
                     hipLaunchKernelGGL((k_primary_persist<SE, 0, true>), dim3(nb), dim3(YRT_PRIMARY_SP_BLOCK), 0,
                                        stream, ds.view, A, C, B, counters);
-                else if (stage && YRT_PRIMARY_REL) {
+                else if (stage) {
                     hipLaunchKernelGGL((k_primary_persist<SE, YRT_PRIMARY_LDS_RECORDS, false>), dim3(nb),
                                        dim3(YRT_PRIMARY_SP_BLOCK), 0, stream, ds.view, A, C, B, counters);
                     ds.last_lds_staging |= 1;
@@ -3260,16 +3075,13 @@ hipError_t run(device_scene& ds, const dev_render_args& A, float4* out, unsigned
                 dim3 sg(level ? stride_grid * WF_BLOCK / TB : tgrid, ds.nlights);
                 if (level == 0 && shadow_persist && B.bundles) {  // the bundles' candidate lists
                     t = T.begin(phase_lists, stream);
-                    if (YRT_BUNDLE_FUSED && YRT_BUNDLE_SUPER && bundle_g * super_bundles <= 256) {
-                        const long long ns = (long long)super_count(nsamp) * ds.nlights;
+                    const long long ns = (long long)super_count(nsamp) * ds.nlights;
+                    if (YRT_BUNDLE_FUSED) {
                         hipLaunchKernelGGL(k_bundle_lists<true>, dim3((unsigned)ns), dim3(256), 0, stream, ds.view, B,
                                            tgrid);
                     } else {
-                        if (YRT_BUNDLE_SUPER) {
-                            const long long ns = (long long)super_count(nsamp) * ds.nlights;
-                            hipLaunchKernelGGL(k_bundle_super, dim3((unsigned)((ns + 3) / 4)), dim3(256), 0, stream,
-                                               ds.view, B, tgrid);
-                        }
+                        hipLaunchKernelGGL(k_bundle_super, dim3((unsigned)((ns + 3) / 4)), dim3(256), 0, stream,
+                                           ds.view, B, tgrid);
                         const long long nw = (long long)bundle_count(nsamp) * ds.nlights;
                         hipLaunchKernelGGL(k_bundle_lists<false>, dim3((unsigned)((nw + 3) / 4)), dim3(256), 0, stream,
                                            ds.view, B, tgrid);
