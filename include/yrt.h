@@ -345,6 +345,45 @@ int yrt_render_passes(yrt_scene* ds, const yrt_render_params* p, unsigned mask, 
 int yrt_shade_rays(yrt_scene* ds, const yrt_render_params* p, const float* rays, int n, float* out_rgba, int mem,
                    void* stream);
 
+/* ---- light groups: one beauty plane per set of lights, from one render ----
+ * Light k is the k-th instance in scene order whose material has ke > 0 in every component
+ * (raytrace.cpp:126). group_of[nlights] (host memory, copied during the call) gives each light
+ * its group in [0, ngroups), or -1 for a light that is in no plane; 1 <= ngroups <=
+ * YRT_LIGHT_GROUPS_MAX. Per camera sample, plane g's value is shade() (raytrace.cpp:88-211)
+ * with the light loop over the lights of group g only, in scene order, from c = +0, and with
+ * la = {0,0,0} * kd; the mirror term is that same function of the mirror ray, times kr (0 * kr
+ * where max_depth cuts it); a miss is {0,0,0,1}. The ambient plane is the same recursion with no
+ * light and la = ambient * kd. Each plane is the beauty's box filter of its value. So group g's
+ * plane has the bits yrt_render writes for the scene in which every light outside g has ke = 0,
+ * rendered with ambient 0; the ambient plane those of the scene with every ke = 0 and the
+ * caller's ambient; `beauty` those of yrt_render for the same `p`, from the same walk; and the
+ * beauty is the sum of the planes up to float32 rounding (the image is linear in each ke and in
+ * the ambient). A shadow ray answered without a walk (yrt_stats.shadow_rays_culled) counts as
+ * occluded, as in yrt_render. (Materials with a non-finite kd are outside this contract.)
+ * Every field of `p` means what it means in yrt_render, except that the algorithm is
+ * YRT_ALGO_WAVEFRONT or YRT_ALGO_WAVEFRONT_LANE and count_work is 0 (otherwise
+ * YRT_ERR_UNSUPPORTED). Planes have yrt_render's layout (row-major window, out_stride; padding
+ * columns keep the caller's bytes); host planes make the call synchronous, device planes are
+ * stream-ordered; an empty window leaves them untouched. A null handle, p, group_of or out,
+ * nlights other than the scene's light count, ngroups outside 1..8, a group_of entry outside
+ * [-1, ngroups), a null plane among the first ngroups or a bad `mem` return
+ * YRT_ERR_INVALID_ARG before any device call. A scene without lights takes nlights = 0; its
+ * group planes, like an empty group's, are black with .w = 1. yrt_last_stats and
+ * yrt_last_timings report what they report after yrt_render of the same `p` (every shadow ray
+ * walked once, depth_truncated counted once), the group shading under YRT_PHASE_SHADE and the
+ * per-pixel sums under YRT_PHASE_ACCUMULATE. The tile-list mode and the LDS staging do not
+ * change the planes. */
+#define YRT_LIGHT_GROUPS_MAX 8
+/* instance index (scene order) of each light, in light order; n = their count. inst may be NULL (count only) */
+int yrt_host_scene_lights(const yrt_host_scene* hs, int* inst, int cap, int* n);
+typedef struct yrt_light_group_planes {
+    float* group[YRT_LIGHT_GROUPS_MAX]; /* the first ngroups must be non-null */
+    float* ambient;                     /* may be NULL */
+    float* beauty;                      /* may be NULL */
+} yrt_light_group_planes;
+int yrt_render_light_groups(yrt_scene* ds, const yrt_render_params* p, const int* group_of, int nlights,
+                            int ngroups, const yrt_light_group_planes* out, int mem, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

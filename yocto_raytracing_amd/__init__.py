@@ -23,7 +23,8 @@ from . import _native as N
 from ._native import RenderParams, Stats, YrtError, check
 
 __all__ = [
-    "Scene", "DeviceScene", "load_scene", "build_bvh", "raytrace", "render_aovs", "render_passes", "intersect_first",
+    "Scene", "DeviceScene", "load_scene", "build_bvh", "raytrace", "render_aovs", "render_passes", "render_light_groups",
+    "intersect_first",
     "intersect_any", "shade_rays", "tonemap", "save_hdr_or_ldr", "render_params", "device_count", "YrtError",
 ]
 
@@ -133,6 +134,15 @@ class Scene:
         buf = (C.c_longlong * 12)()
         check(N.lib.yrt_host_scene_info(self._h, buf), "yrt_host_scene_info")
         return dict(zip(INFO_FIELDS, list(buf)))
+
+    def lights(self) -> list:
+        """the instance index (scene order) of each light, in light order: the instances whose
+        material has ke > 0 in every component (raytrace.cpp:126)"""
+        n = C.c_int()
+        check(N.lib.yrt_host_scene_lights(self._h, None, 0, C.byref(n)), "yrt_host_scene_lights")
+        inst = (C.c_int * max(n.value, 1))()
+        check(N.lib.yrt_host_scene_lights(self._h, inst, n.value, C.byref(n)), "yrt_host_scene_lights")
+        return list(inst[:n.value])
 
     def image_size(self, resolution: int, camera: int = 0):
         w, h = C.c_int(), C.c_int()
@@ -247,6 +257,23 @@ class DeviceScene:
         mem = N.YRT_MEM_DEVICE if device_memory else N.YRT_MEM_HOST
         check(N.lib.yrt_render_passes(self._h, C.byref(params), mask, C.byref(pp), C.c_void_p(beauty_ptr or 0), mem,
                                       C.c_void_p(stream or 0)), "yrt_render_passes")
+
+    def render_light_groups_into(self, params: RenderParams, groups: Sequence[int], group_ptrs: Sequence[int],
+                                 ambient_ptr: Optional[int] = None, beauty_ptr: Optional[int] = None,
+                                 device_memory: bool = True, stream: Optional[int] = None) -> None:
+        """Launch raytrace() split by light group (yrt_render_light_groups): `groups` gives each of
+        the scene's lights (Scene.lights() order) its group, -1 for none; `group_ptrs` one plane
+        per group, RGBA float32 in render_into's layout; `ambient_ptr` and `beauty_ptr`, when
+        given, receive the ambient term's plane and render_into's image from the same walk."""
+        ngroups = _light_groups(groups, len(group_ptrs))
+        lp = N.LightGroupPlanes()
+        for g, ptr in enumerate(group_ptrs):
+            lp.group[g] = ptr
+        lp.ambient, lp.beauty = ambient_ptr or None, beauty_ptr or None
+        gof = (C.c_int * max(len(groups), 1))(*[int(g) for g in groups])
+        mem = N.YRT_MEM_DEVICE if device_memory else N.YRT_MEM_HOST
+        check(N.lib.yrt_render_light_groups(self._h, C.byref(params), gof, len(groups), ngroups, C.byref(lp), mem,
+                                            C.c_void_p(stream or 0)), "yrt_render_light_groups")
 
     def shade_rays_into(self, params: RenderParams, rays_ptr: int, n: int, out_ptr: int, device_memory: bool = True,
                         stream: Optional[int] = None) -> None:
@@ -474,6 +501,57 @@ def render_passes(scn, amb: Sequence[float] = (0.1, 0.1, 0.1), resolution: int =
                           beauty_ptr=img.ctypes.data if beauty else None, device_memory=False)
     if beauty:
         out["beauty"] = img
+    return out
+
+
+def _light_groups(groups, ngroups: Optional[int] = None) -> int:
+    """the number of groups `groups` names (each entry a group in [0, YRT_LIGHT_GROUPS_MAX) or
+    -1; at least one group); a bad entry raises before any native call"""
+    gs = list(groups)
+    for g in gs:
+        if not isinstance(g, (int, np.integer)) or isinstance(g, bool) or g < -1 or g >= N.YRT_LIGHT_GROUPS_MAX:
+            raise ValueError(f"light group {g!r}: an integer from -1 (no plane) to {N.YRT_LIGHT_GROUPS_MAX - 1}")
+    need = max([int(g) for g in gs] + [0]) + 1
+    if ngroups is None:
+        return need
+    if not need <= ngroups <= N.YRT_LIGHT_GROUPS_MAX:
+        raise ValueError(f"{ngroups} planes for light groups 0..{need - 1} (at most {N.YRT_LIGHT_GROUPS_MAX})")
+    return ngroups
+
+
+def render_light_groups(scn, amb: Sequence[float] = (0.1, 0.1, 0.1), resolution: int = 720, samples: int = 1, *,
+                        groups: Sequence[int], ambient: bool = True, beauty: bool = True, width: int = 0,
+                        max_depth: int = 16, camera: int = 0, window=None, algorithm: str = "wavefront",
+                        devices=None, device: int = 0) -> dict:
+    """raytrace split by light: `groups` gives each light of the scene (Scene.lights() order) its
+    group, 0 to 7, or -1 for a light that is in no plane. Returns {"groups": [(H, W, 4) float32 per
+    group], "ambient": ..., "beauty": ...} from one render: a group's plane is the image its lights
+    alone produce (mirror reflections included, ambient 0), "ambient" the image of the ambient term
+    alone, "beauty" the image raytrace gives. The image is linear in each light's ke and in the
+    ambient, so the beauty is the sum of the planes up to float32 rounding and a light can be
+    rescaled or recoloured without tracing a ray. One GPU: `devices` is not supported."""
+    ngroups = _light_groups(groups)
+    if devices is not None:
+        raise ValueError("render_light_groups renders on one GPU: devices= is not supported")
+    host = scn.host if isinstance(scn, DeviceScene) else scn
+    if len(list(groups)) != len(host.lights()):
+        raise ValueError(f"groups names {len(list(groups))} lights, the scene has {len(host.lights())}")
+    ds = _device_scene(scn, device)
+    p = render_params(amb, resolution, samples, width=width, max_depth=max_depth, camera=camera, window=window,
+                      algorithm=algorithm)
+    W, H = ds.image_size(p)
+    if window is None:
+        w, h = W, H
+    else:
+        w, h = window[2] or W - window[0], window[3] or H - window[1]
+    out = {"groups": [np.zeros((h, w, 4), np.float32) for _ in range(ngroups)]}
+    if ambient:
+        out["ambient"] = np.zeros((h, w, 4), np.float32)
+    if beauty:
+        out["beauty"] = np.zeros((h, w, 4), np.float32)
+    ds.render_light_groups_into(p, list(groups), [a.ctypes.data for a in out["groups"]],
+                                ambient_ptr=out["ambient"].ctypes.data if ambient else None,
+                                beauty_ptr=out["beauty"].ctypes.data if beauty else None, device_memory=False)
     return out
 
 

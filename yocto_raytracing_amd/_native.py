@@ -106,6 +106,14 @@ class PassPlanes(C.Structure):
     _fields_ = [("plane", C.c_void_p * YRT_PASS_COUNT)]
 
 
+# yrt_render_light_groups: one plane per group of lights, the ambient plane, the beauty
+YRT_LIGHT_GROUPS_MAX = 8
+
+
+class LightGroupPlanes(C.Structure):
+    _fields_ = [("group", C.c_void_p * YRT_LIGHT_GROUPS_MAX), ("ambient", C.c_void_p), ("beauty", C.c_void_p)]
+
+
 _vp = C.c_void_p
 _ip =C.POINTER(C.c_int)
 _sig = {
@@ -156,6 +164,9 @@ _sig = {
     "yrt_render_aovs": (C.c_int, [_vp, C.POINTER(RenderParams), C.c_uint, C.POINTER(AovPlanes), C.c_int, _vp]),
     "yrt_render_passes": (C.c_int, [_vp, C.POINTER(RenderParams), C.c_uint, C.POINTER(PassPlanes), _vp, C.c_int, _vp]),
     "yrt_shade_rays": (C.c_int, [_vp, C.POINTER(RenderParams), _vp, C.c_int, _vp, C.c_int, _vp]),
+    "yrt_host_scene_lights": (C.c_int, [_vp, _ip, C.c_int, _ip]),
+    "yrt_render_light_groups": (C.c_int, [_vp, C.POINTER(RenderParams), _ip, C.c_int, C.c_int,
+                                          C.POINTER(LightGroupPlanes), C.c_int, _vp]),
 }
 EXPORTS = tuple(_sig)
 

@@ -247,6 +247,22 @@ int yrt_host_scene_info(const yrt_host_scene* hs, long long* info) {
     });
 }
 
+int yrt_host_scene_lights(const yrt_host_scene* hs, int* inst, int cap, int* n) {
+    if (!hs || !n || (inst && cap < 0)) return YRT_ERR_INVALID_ARG;
+    // (the lights of device_scene_create, in its order: raytrace.cpp:126)
+    int count = 0;
+    const auto& s = hs->scn;
+    for (size_t k = 0; k < s.instances.size(); k++) {
+        if (s.instances[k].mat < 0) continue;
+        const auto ke = s.materials[s.instances[k].mat].ke;
+        if (!(ke.x > 0.0f && ke.y > 0.0f && ke.z > 0.0f)) continue;
+        if (inst && count < cap) inst[count] = (int)k;
+        count++;
+    }
+    *n = count;
+    return YRT_OK;
+}
+
 int yrt_host_image_size(const yrt_host_scene* hs, int camera, int resolution, int* w, int* h) {
     if (!hs || !w || !h || camera < 0 || camera >= (int)hs->scn.cameras.size() || resolution <= 0)
         return YRT_ERR_INVALID_ARG;
@@ -684,6 +700,105 @@ int yrt_render_passes(yrt_scene* s, const yrt_render_params* p, unsigned mask, c
             if (host[k]) e = hipMemcpyAsync(host[k], dev[k], bytes, hipMemcpyDeviceToHost, st);
         const hipError_t e2 = hipStreamSynchronize(st);
         hip_check(e, "passes render");
+        hip_check(e2, "hipStreamSynchronize");
+        return YRT_OK;
+    });
+}
+
+static_assert(YRT_LIGHT_GROUPS_MAX == yrt::light_groups_max, "the kernel's plane count is the header's");
+
+int yrt_render_light_groups(yrt_scene* s, const yrt_render_params* p, const int* group_of, int nlights, int ngroups,
+                            const yrt_light_group_planes* out, int mem, void* stream) {
+    if (!s || !p || !group_of || !out) return YRT_ERR_INVALID_ARG;
+    auto refuse = [](const char* why) {
+        g_last_error = why;
+        return YRT_ERR_INVALID_ARG;
+    };
+    if (ngroups < 1 || ngroups > YRT_LIGHT_GROUPS_MAX) return refuse("light groups: ngroups must be 1 to YRT_LIGHT_GROUPS_MAX");
+    if (nlights < 0) return refuse("light groups: nlights is negative");
+    for (int k = 0; k < nlights; k++)
+        if (group_of[k] < -1 || group_of[k] >= ngroups) return refuse("light groups: a group_of entry is outside [-1, ngroups)");
+    for (int g = 0; g < ngroups; g++)
+        if (!out->group[g]) return refuse("light groups: a group's plane is null");
+    if (mem != YRT_MEM_HOST && mem != YRT_MEM_DEVICE) return refuse("light groups: mem is YRT_MEM_HOST or YRT_MEM_DEVICE");
+    if (!s->ds || nlights != s->ds->nlights) return refuse("light groups: nlights is not the scene's light count");
+    return guarded([&] {
+        if (p->algorithm == YRT_ALGO_MEGAKERNEL) throw yrt::unsupported_error("light groups run in the wavefront algorithms");
+        if (p->algorithm != YRT_ALGO_WAVEFRONT && p->algorithm != YRT_ALGO_WAVEFRONT_LANE)
+            throw std::invalid_argument("unknown algorithm");
+        if (p->count_work != 0) throw yrt::unsupported_error("light groups do not count work");
+        auto r = resolve(*s->ds, *p);
+        hipStream_t st = (hipStream_t)stream;
+        hip_check(hipSetDevice(s->ds->device), "hipSetDevice");
+        yrt::dev_render_args a = {};
+        a.cam = yrt::make_dev_camera(s->ds->cameras[p->camera]);
+        for (int k = 0; k < 3; k++) a.amb[k] = p->ambient[k];
+        a.width = r.W;
+        a.height = r.H;
+        a.samples = p->samples;
+        a.max_depth = p->max_depth > 0 ? p->max_depth : 16;
+        a.x0 = r.x0;
+        a.tile_w = r.tw;
+        a.y0 = r.y0;
+        a.tile_h = r.th;
+        a.band = p->band;
+        a.band_stride = p->band_stride;
+        a.band_offset = p->band_offset;
+        a.out_stride = p->out_stride > 0 ? p->out_stride : r.tw;
+        if (a.out_stride < r.tw) throw std::invalid_argument("out_stride smaller than the window width");
+        if (!(p->timing == 2 && s->ds->timer.on)) s->ds->timer.reset(p->timing != 0);
+        const bool packet = p->algorithm == YRT_ALGO_WAVEFRONT;
+        s->last_stream = st;
+        // the caller's planes in one list: the groups, the ambient, the beauty
+        constexpr int NP = YRT_LIGHT_GROUPS_MAX + 2;
+        float* host[NP] = {};
+        for (int g = 0; g < ngroups; g++) host[g] = out->group[g];
+        host[NP - 2] = out->ambient, host[NP - 1] = out->beauty;
+        auto planes_of = [&](float* const* v) {
+            yrt::dev_light_group_planes dp = {};
+            for (int g = 0; g < ngroups; g++) dp.group[g] = v[g];
+            dp.ambient = v[NP - 2], dp.beauty = v[NP - 1];
+            return dp;
+        };
+        if (mem == YRT_MEM_DEVICE || r.tw <= 0 || r.th <= 0) {
+            // (an empty window launches nothing but the counters' memset: the planes are not touched)
+            hip_check(yrt::launch_render_wavefront_light_groups(*s->ds, a, group_of, ngroups, planes_of(host), s->counters,
+                                                                packet, st),
+                      "light groups render launch");
+            return YRT_OK;
+        }
+        // host planes: device staging of their own (the handle's scratch stays yrt_render's),
+        // copied back and released
+        const size_t bytes = (size_t)a.out_stride * r.th * 16;
+        struct staging {
+            void* p = nullptr;
+            ~staging() {
+                if (p) (void)hipFree(p);
+            }
+        } stage;
+        size_t used = 0;
+        for (int k = 0; k < NP; k++) used += host[k] ? 1 : 0;
+        hip_check(hipMalloc(&stage.p, bytes * used), "hipMalloc(light group staging)");
+        float* dev[NP] = {};
+        used = 0;
+        for (int k = 0; k < NP; k++)
+            if (host[k]) dev[k] = (float*)((char*)stage.p + bytes * used++);
+        // padding columns (out_stride > tile_w) keep the caller's bytes: they are staged too
+        if (a.out_stride > r.tw)
+            for (int k = 0; k < NP; k++)
+                if (host[k]) hip_check(hipMemcpyAsync(dev[k], host[k], bytes, hipMemcpyHostToDevice, st), "hipMemcpyAsync");
+        hipError_t e = hipSuccess;
+        try {
+            e = yrt::launch_render_wavefront_light_groups(*s->ds, a, group_of, ngroups, planes_of(dev), s->counters, packet,
+                                                          st);
+        } catch (...) {
+            (void)hipStreamSynchronize(st);  // the staging is released only after the stream has drained
+            throw;
+        }
+        for (int k = 0; k < NP && e == hipSuccess; k++)
+            if (host[k]) e = hipMemcpyAsync(host[k], dev[k], bytes, hipMemcpyDeviceToHost, st);
+        const hipError_t e2 = hipStreamSynchronize(st);
+        hip_check(e, "light groups render");
         hip_check(e2, "hipStreamSynchronize");
         return YRT_OK;
     });

@@ -7,7 +7,9 @@
 // the reference): --device N, --width W, --max-depth D, --algorithm
 // wavefront|megakernel|wavefront_lane, --time (print GPU time and Mrays/s), --aov LIST
 // (the camera hit's geometry buffers as .npy files beside the image), --passes LIST (the
-// image's lighting split, from the same render, as .npy files beside it).
+// image's lighting split, from the same render, as .npy files beside it), --light-groups LIST
+// (one plane per group of lights and the ambient plane, from the same render, as .npy files).
+#include <algorithm>
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -37,7 +39,11 @@ namespace {
             "                       depth,position,normal,texcoord,albedo,ids (one GPU)\n"
             "  --passes LIST        also write OUT.<name>.npy, (H, W, 4) float32, for each of\n"
             "                       direct,diffuse,specular,reflection,ambient, from the image's own render\n"
-            "                       (one GPU, a wavefront algorithm)\n");
+            "                       (one GPU, a wavefront algorithm)\n"
+            "  --light-groups LIST  one entry per light of the scene, in scene order: its group, 0 to 7, or -1\n"
+            "                       for none, e.g. 0,1,0,-1,2; also write OUT.group<g>.npy per group (the image\n"
+            "                       its lights alone produce) and OUT.ambient.npy, (H, W, 4) float32, from the\n"
+            "                       image's own render (one GPU, a wavefront algorithm)\n");
     exit(msg ? 1 : 0);
 }
 
@@ -84,6 +90,24 @@ unsigned parse_passes(const std::string& list) {
     return mask;
 }
 
+// --light-groups' comma-separated group of each light
+std::vector<int> parse_light_groups(const std::string& list) {
+    std::vector<int> groups;
+    for (size_t at = 0; at <= list.size();) {
+        size_t end = list.find(',', at);
+        if (end == std::string::npos) end = list.size();
+        const std::string item = list.substr(at, end - at);
+        char* stop = nullptr;
+        const long g = strtol(item.c_str(), &stop, 10);
+        if (item.empty() || *stop) usage(("bad --light-groups entry '" + item + "'").c_str());
+        if (g < -1 || g >= YRT_LIGHT_GROUPS_MAX)
+            usage(("--light-groups entry " + item + " is out of range: -1 (no plane) or a group from 0 to 7").c_str());
+        groups.push_back((int)g);
+        at = end + 1;
+    }
+    return groups;
+}
+
 // a (h, w, 4) array of 4-byte elements as a NumPy format 1.0 file, C order: the magic, the
 // version, the header dict's length, the dict padded with spaces so that the data starts on
 // a multiple of 64 bytes, a newline, the data
@@ -108,6 +132,8 @@ int main(int argc, char** argv) {
     float amb = 0.1f;
     bool timing = false;
     unsigned aovs = 0, passes = 0;
+    std::vector<int> light_groups;
+    bool groups = false;
     std::string out = "out.png", scenein;
     for (int k = 1; k < argc; k++) {
         std::string a = argv[k];
@@ -132,6 +158,7 @@ int main(int argc, char** argv) {
         } else if (a == "--time") timing = true;
         else if (a == "--aov") aovs = parse_aovs(val());
         else if (a == "--passes") passes = parse_passes(val());
+        else if (a == "--light-groups") light_groups = parse_light_groups(val()), groups = true;
         else if (a == "-h" || a == "--help") usage(nullptr);
         else if (!a.empty() && a[0] == '-') usage(("unknown option " + a).c_str());
         else if (scenein.empty()) scenein = a;
@@ -142,9 +169,20 @@ int main(int argc, char** argv) {
     if (aovs && gpus > 1) usage("--aov renders on one GPU (--gpus 1)");
     if (passes && gpus > 1) usage("--passes renders on one GPU (--gpus 1)");
     if (passes && algorithm == YRT_ALGO_MEGAKERNEL) usage("--passes needs a wavefront algorithm, not --algorithm megakernel");
+    if (groups && gpus > 1) usage("--light-groups renders on one GPU (--gpus 1)");
+    if (groups && algorithm == YRT_ALGO_MEGAKERNEL)
+        usage("--light-groups needs a wavefront algorithm, not --algorithm megakernel");
+    if (groups && passes) usage("--light-groups and --passes are renders of their own: give one of them");
     try {
         printf("loading scene %s\n", scenein.c_str());
         auto scn = yrt_cpp::load_scene(scenein);
+        if (groups) {
+            int nlights = 0;
+            yrt_cpp::check(yrt_host_scene_lights(scn->host, nullptr, 0, &nlights), "lights");
+            if ((int)light_groups.size() != nlights)
+                usage(("--light-groups names " + std::to_string(light_groups.size()) + " lights, the scene has " +
+                       std::to_string(nlights)).c_str());
+        }
         printf("creating bvh\n");
         yrt_cpp::build_bvh(scn, false);
         scn->device = device;
@@ -158,6 +196,9 @@ int main(int argc, char** argv) {
         const std::string stem =
             dot != std::string::npos && (slash == std::string::npos || dot > slash) ? out.substr(0, dot) : out;
         std::vector<std::vector<float>> pass_data(YRT_PASS_COUNT);
+        int ngroups = 1;
+        for (int g : light_groups) ngroups = std::max(ngroups, g + 1);
+        std::vector<std::vector<float>> group_data(groups ? ngroups + 1 : 0);  // the groups, then the ambient
         auto t0 = std::chrono::steady_clock::now();
         yrt_cpp::image4f hdr;
         if (passes) {
@@ -177,6 +218,24 @@ int main(int argc, char** argv) {
                 }
             yrt_cpp::check(yrt_render_passes(scn->on_device(), &p, passes, &pp, &hdr.pixels[0].x, YRT_MEM_HOST, nullptr),
                            "render_passes");
+        } else if (groups) {
+            // one render: the image, its light groups and the ambient plane in host memory
+            yrt_render_params p = scn->params;
+            p.ambient[0] = p.ambient[1] = p.ambient[2] = amb;
+            p.resolution = resolution;
+            p.samples = samples;
+            int w = 0, h = 0;
+            yrt_cpp::check(yrt_image_size(scn->on_device(), &p, &w, &h), "raytrace");
+            hdr = yrt_cpp::image4f(w, h);
+            yrt_light_group_planes lp = {};
+            for (auto& d : group_data) d.resize((size_t)w * h * 4);
+            for (int g = 0; g < ngroups; g++) lp.group[g] = group_data[g].data();
+            lp.ambient = group_data[ngroups].data();
+            lp.beauty = &hdr.pixels[0].x;
+            const int none = -1;  // (a scene without lights: the list is empty, the pointer still given)
+            yrt_cpp::check(yrt_render_light_groups(scn->on_device(), &p, light_groups.empty() ? &none : light_groups.data(),
+                                                   (int)light_groups.size(), ngroups, &lp, YRT_MEM_HOST, nullptr),
+                           "render_light_groups");
         } else
             hdr = yrt_cpp::raytrace(scn, {amb, amb, amb}, resolution, samples);
         auto t1 = std::chrono::steady_clock::now();
@@ -193,6 +252,9 @@ int main(int argc, char** argv) {
         for (int k = 0; k < YRT_PASS_COUNT; k++)
             if (passes >> k & 1)
                 save_npy(stem + "." + pass_names[k] + ".npy", pass_data[k].data(), hdr.width, hdr.height, "<f4");
+        for (size_t g = 0; g < group_data.size(); g++)
+            save_npy(stem + (g + 1 < group_data.size() ? ".group" + std::to_string(g) : std::string(".ambient")) + ".npy",
+                     group_data[g].data(), hdr.width, hdr.height, "<f4");
         if (aovs) {
             // the requested planes in host memory, each saved as <output without extension>.<name>.npy
             yrt_render_params p = scn->params;

@@ -2021,7 +2021,9 @@ __global__ __launch_bounds__(SP_BLOCK, YRT_SHADOW_WAVES) void k_shadow_persist(d
 // material, the textures, the lights that are not occluded, the mirror branch. Every kernel
 // that shades calls this one body (k_shade, k_rays_shade, k_shade_passes and
 // k_shadow_shade_persist's epilogue): the image, the ray batches and the passes are bit-exact
-// because they run the same operations in the same order.
+// because they run the same operations in the same order. (Two kernels write these statements
+// out in a body of their own and are to be changed with this one: the fused k_shade_passes, and
+// k_shade_groups, whose light loop runs once per plane over the plane's lights.)
 // OCC4: the lights' occlusion is the mask occ_bits, else the bytes B.occl.
 // LATE (k_shadow_shade_persist, at the any-hit grid's 64 VGPRs): what only the end needs, la and
 // kr and the reflective flag, is computed or loaded again after the light loop instead of held
@@ -2564,6 +2566,256 @@ __global__ __launch_bounds__(SB, FUSE ? shade_pass_waves : YRT_SHADE_LEVEL_WAVES
     flush(counters, cnt_depth_truncated, truncated);
 }
 
+// ---- light groups (yrt_render_light_groups): one walk, one beauty plane per set of lights ----
+// A plane is the image of a scene variant: plane k's shade() runs the light loop over its own
+// lights only, in scene order, from c = +0, and adds la = amb * kd only where the plane has the
+// ambient term. A group plane has its group's lights and no ambient; the ambient plane no light
+// and the caller's ambient; the beauty every light and the ambient. The closest hits, the shadow
+// rays' answers and the mirror rays (the spawn depends on kr alone) are the same for every
+// plane, so they are made once; what differs is the light loop, the fold and the per-pixel sum.
+// The planes are shaded group-major with ONE accumulator: per sample the surface, the material,
+// the textures and v once, then per plane c = +0, that plane's lights (the host sorts them by
+// plane, stably, into `tab`; the indices do not depend on the lane and are scalar reads), and c
+// -- or the value folded from it -- leaves for plane k before the next plane starts. Inside a
+// plane the additions are shade_hit's in shade_hit's order, so a plane has the bits yrt_render
+// writes for its variant. A plane without the ambient term skips the mirror fold's `+ la`: its
+// la is (0 * kd) * texel, +0 or -0 for a finite kd, and the sum it would be added to is never
+// -0 (it ends in an addition to c, which starts at +0), so the bits are the same; level 0's
+// `+ la` and the `0 * kr` of a cut mirror ray are computed as written.
+// k_shade_groups has a body of its own, like the fused k_shade_passes: shade_hit keeps one c
+// per call. A change to shade_hit is to be made here too (tests/test_gpu_light_groups.py
+// compares every plane with yrt_render of its variant bit for bit).
+constexpr int group_planes = light_groups_max + 2;  // the groups, the ambient, the beauty
+struct group_buffers {
+    int nplanes;              // planes in use, [0, nplanes)
+    unsigned amb_mask;        // bit k: plane k adds la (the ambient plane and the beauty)
+    // behind the workspace: tab[k], tab[k + 1] bound plane k's entries of tab + group_planes + 1,
+    // each the index of a light
+    const int* tab;
+    float4* out[group_planes];  // the caller's planes (window layout, out_stride)
+    f4* smp[group_planes];      // per-sample values (unfused and mirror shapes); plane 0's is B.rad
+    // mirror levels: plane k's {c.xyz, material index} of level l at rec[k] + l * capacity (plane
+    // 0's is B.rec0_); la, the same for every plane that adds it, is B.rec1
+    f4* rec[group_planes];
+};
+
+// Fused (one level, whole pixels per block): the per-sample values go to LDS rows of SB + 1
+// floats per (plane, component), 30.8 KB for the ten planes; with the sRGB table a block takes
+// 31.9 KB, five blocks fit a CU's 160 KB: 5 waves per SIMD, the kernel's launch bound.
+constexpr int shade_group_waves = 5;
+template <bool FUSE, int SB = WF_BLOCK, bool OCC4 = false>
+__global__ __launch_bounds__(SB, shade_group_waves) void k_shade_groups(dev_scene_view S, dev_render_args A, int level,
+                                                                        int nsamp_level0, int max_depth, wf_buffers B,
+                                                                        group_buffers G, unsigned long long* counters,
+                                                                        chunk_args C) {
+    constexpr int ROW = SB + 1;
+    __shared__ float fused[FUSE ? group_planes * 3 * ROW : 1];
+    __shared__ int cmp_count[SB / 64], cmp_base[SB / 64];
+    __shared__ srgb_table srgb_lds;
+    const float* lut = stage_srgb<SB, true>(S, srgb_lds);
+    work_counts wc;
+    unsigned long long truncated = 0;
+    // (the ambient and the view point as scalars of their own, not as parts of the eight-dword
+    // kernel-argument loads that bring them in: such a tuple, live across the kernel, left an
+    // unused 32-byte spill slot, and with it a private segment, behind)
+    float amb_x = A.amb[0], amb_y = A.amb[1], amb_z = A.amb[2];
+    float cam_x = A.cam.ox, cam_y = A.cam.oy, cam_z = A.cam.oz;
+    asm volatile("" : "+s"(amb_x), "+s"(amb_y), "+s"(amb_z), "+s"(cam_x), "+s"(cam_y), "+s"(cam_z));
+    const vec3f amb = {amb_x, amb_y, amb_z};
+    const vec3f cam_o = {cam_x, cam_y, cam_z};
+    const int nplanes = G.nplanes;
+    const int* order = G.tab + group_planes + 1;
+    const int stride = gridDim.x * SB;
+    const int gout = (int)(blockIdx.x % (unsigned)level_segments);
+    const int nseg = FUSE ? 1 : level ? level_segments : 1;
+    for (int g = 0; g < nseg; g++) {
+    const int n = (!FUSE && level) ? *seg_counter(B.count, level, g) : nsamp_level0;
+    const int nround = (n + stride - 1) / stride;
+    for (int round = 0; round < nround; round++) {
+        const int j = round * stride + blockIdx.x * SB + threadIdx.x;
+        const int idx = FUSE ? j : g * B.seg + j;
+        // what does not depend on the plane, once per sample
+        bool hit = false, write_r = false, spawn = false, reflective = false;
+        vec3f p = {0, 0, 0}, nrm = {0, 0, 0}, v = {0, 0, 0}, dr = {0, 0, 0};
+        vec3f kd = {0, 0, 0}, ks = {0, 0, 0}, kr = {0, 0, 0}, la = {0, 0, 0}, la0 = {0, 0, 0}, t = {0, 0, 0};
+        float ns = 0.0f;
+        int mat = 0, kind = 0;
+        uint32_t occ_bits = 0;
+        if (j < n) {
+            const float4 s0 = ld4s(B.surf0 + idx);
+            if constexpr (OCC4) {
+                // (four unconditional loads, a light past the scene's reading light 0's byte;
+                // only the bits of the plane's own lights are looked at)
+#pragma unroll
+                for (int q = 0; q < 4; q++) {
+                    const int lq = q < S.nlights ? q : 0;
+                    occ_bits |= (ldb(B.occl + (size_t)lq * B.capacity + idx) != 0u ? 1u : 0u) << q;
+                }
+            }
+            const int info = sample_state(s0);
+            write_r = info != -2;
+            hit = info >= 0;
+            if (hit) {
+                // level >= 1: this sample's ray record {origin, parent index}
+                const float4 ro4 =
+                    (!FUSE && level) ? ld4(B.ray_o(level) + idx) : make_float4(cam_o.x, cam_o.y, cam_o.z, 0.0f);
+                vec2f uv;
+                {
+                    const float4 s1 = ld4s(B.surf1 + idx);
+                    p = xyz(s0), nrm = xyz(s1), uv = {s1.w, B.need_v ? lds1(B.surfv + idx) : 0.0f};
+                    mat = info_mat(info), kind = info & 3;
+                }
+                const vec3f ro = xyz(ro4);
+                const float4 m0 = ld4(S.mats + 4 * mat), m1 = ld4(S.mats + 4 * mat + 1);
+                const float4 m2 = ld4(S.mats + 4 * mat + 2), m3 = ld4(S.mats + 4 * mat + 3);
+                const vec3f kd0 = xyz(m0), ks0 = xyz(m1);
+                kr = xyz(m2), ns = m0.w;
+                const int kd_txt = ibits(m1.w), ks_txt = ibits(m2.w);
+                reflective = ibits(m3.w) & mat_reflective;
+                const vec3f zero = {0.0f, 0.0f, 0.0f};
+                la = amb * kd0, la0 = zero * kd0;
+                vec3f tkd = {1, 1, 1}, tks = {1, 1, 1};
+                if (kd_txt >= 0) {
+                    tkd = eval_texture<false>(S, kd_txt, uv, wc, lut);
+                    la = la * tkd, la0 = la0 * tkd;
+                }
+                if (ks_txt >= 0) tks = eval_texture<false>(S, ks_txt, uv, wc, lut);
+                // (shade_hit forms kd and ks per light, from the same operands each time)
+                kd = kd0, ks = ks0;
+                if (kd_txt >= 0) kd = kd * tkd;
+                if (ks_txt >= 0) ks = ks * tks;
+                float vlen;
+                normalize_len(ro - p, v, vlen);
+                if (reflective) {
+                    if (FUSE || level + 1 >= max_depth || level + 1 >= B.nlevels) {
+                        // depth cap: the reflected contribution counts as a miss (col = 0); counted once
+                        truncated++;
+                        t = {0.0f * kr.x, 0.0f * kr.y, 0.0f * kr.z};
+                    } else {
+                        spawn = true;
+                        dr = (nrm * 2.0f * dot(nrm, v)) - v;
+                        write_r = false;
+                    }
+                }
+            }
+        }
+        // the planes, one after the other (uniform over the block: every lane walks the table)
+        for (int k = 0; k < nplanes; k++) {
+            const int q0 = __builtin_amdgcn_readfirstlane(G.tab[k]), q1 = __builtin_amdgcn_readfirstlane(G.tab[k + 1]);
+            const bool ambk = G.amb_mask >> k & 1;
+            vec3f R = {0, 0, 0};
+            if (hit) {
+                vec3f c = {0.0f, 0.0f, 0.0f};
+                for (int q = q0; q < q1; q++) {
+                    const int li = __builtin_amdgcn_readfirstlane(order[q]);
+                    if (OCC4 ? ((occ_bits >> li) & 1u) != 0u : ldb(B.occl + (size_t)li * B.capacity + idx) != 0) continue;
+                    float4 lrec[6];
+                    ld_scalar<6>(S.lights + 6 * li, lrec);
+                    frame3f lf = {xyz(lrec[0]), xyz(lrec[1]), xyz(lrec[2]), xyz(lrec[3])};
+                    vec3f lp0 = xyz(lrec[4]), ke = xyz(lrec[5]);
+                    vec3f tp = transform_point(lf, lp0 - p);
+                    vec3f l, h;
+                    float r, hlen;
+                    normalize_len(tp, l, r);
+                    normalize_len(v + l, h, hlen);
+                    const vec3f ker = div3(ke, r * r);
+                    vec3f ld = kd * ker;
+                    vec3f ls = ks * ker;
+                    if (kind == kind_lines) {
+                        float prodnl = dot(nrm, l);
+                        float prodnh = dot(nrm, h);
+                        if (prodnl < 0.0f) prodnl *= -1;
+                        if (prodnh < 0.0f) prodnh *= -1;
+                        float sinnl = __builtin_sqrtf(1.0f - prodnl);
+                        float sinnh = __builtin_sqrtf(1.0f - prodnh);
+                        ld = ld * sinnl;
+                        ls = ls * spec_pow(sinnh, ns, ls);
+                    } else {
+                        ld = ld * smax(0.0f, dot(nrm, l));
+                        ls = ls * spec_pow(smax(0.0f, dot(nrm, h)), ns, ls);
+                    }
+                    c = c + (ld + ls);
+                }
+                const vec3f lak = ambk ? la : la0;
+                if (!reflective)
+                    R = c + lak;
+                else if (!spawn)
+                    R = (c + t) + lak;
+                else
+                    G.rec[k][(size_t)level * B.capacity + idx] = {c.x, c.y, c.z, __int_as_float(mat)};
+            }
+            if constexpr (FUSE) {
+                // (one round per block: the rows are written once; a lane past the chunk writes +0)
+                fused[(k * 3 + 0) * ROW + threadIdx.x] = R.x;
+                fused[(k * 3 + 1) * ROW + threadIdx.x] = R.y;
+                fused[(k * 3 + 2) * ROW + threadIdx.x] = R.z;
+            } else if (write_r) {
+                // a final value at level k >= 1 folds up its chain of parents (raytrace.cpp:201-206,
+                // R_k-1 = (D + R_k * kr) + la) to the camera sample, plane by plane
+                vec3f col = R;
+                int lev = level, node = idx;
+                while (lev > 0) {
+                    const int parent = ibits(B.ray_o(lev)[node].w);
+                    const float4 d = ld4(G.rec[k] + (size_t)(lev - 1) * B.capacity + parent);
+                    const float4 pkr = ld4(S.mats + 4 * ibits(d.w) + 2);  // the parent's material kr
+                    vec3f cc = {d.x, d.y, d.z};
+                    const vec3f tt = {col.x * pkr.x, col.y * pkr.y, col.z * pkr.z};
+                    cc = cc + tt;
+                    if (ambk) cc = cc + xyz(ld4(B.rec1(lev - 1) + parent));
+                    col = cc, node = parent, lev--;
+                }
+                G.smp[k][node] = {col.x, col.y, col.z, 1.0f};
+            }
+        }
+        if constexpr (FUSE) continue;  // one level: no mirror rays
+        // the mirror rays, spawned and compacted once for all planes (shade_samples' compaction)
+        const unsigned long long mask = __ballot(spawn);
+        const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
+        if (spawn) B.rec1(level)[idx] = {la.x, la.y, la.z, 0};
+        if (lane == 0) cmp_count[w] = __popcll(mask);
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            int tot = 0;
+            for (int q = 0; q < SB / 64; q++) tot += cmp_count[q];
+            int acc = tot ? atomicAdd(seg_counter(B.count, level + 1, gout), tot) : 0;
+            for (int q = 0; q < SB / 64; q++) cmp_base[q] = acc, acc += cmp_count[q];
+        }
+        __syncthreads();
+        if (spawn) {
+            const int slot = gout * B.seg + cmp_base[w] + __popcll(mask & ((1ull << lane) - 1));
+            B.ray_o(level + 1)[slot] = {p.x, p.y, p.z, __int_as_float(idx)};
+            B.ray_d(level + 1)[slot] = {dr.x, dr.y, dr.z, 0};
+        }
+    }
+    }
+    if (FUSE) {
+        // raytrace.cpp:232-249 per plane: one lane per (pixel, plane, colour component), each
+        // lane's sum the reference's ordered chain of adds for that component
+        __syncthreads();
+        const int ppb = SB / C.spp;
+        for (int e = (int)threadIdx.x; e < 3 * nplanes * ppb; e += SB) {
+            const int px = e / (3 * nplanes), r = e - 3 * nplanes * px;
+            const int k = r / 3, comp = r - 3 * k;
+            const int pl = (int)(blockIdx.x * SB / C.spp) + px;
+            int lx, ly, i, j;
+            const bool valid = pl < C.npix && pixel_of(A, C, C.pix0 + pl, lx, ly, i, j);
+            if (pl < C.npix && lx < A.tile_w && ly < A.tile_h) {
+                float val = 0.0f;
+                if (valid) {
+                    const float* row = fused + (k * 3 + comp) * ROW + px * C.spp;
+                    float acc = 0.0f;
+                    for (int q = 0; q < C.spp; q++) acc = acc + row[q];
+                    val = acc / float(C.spp);
+                }
+                float* o = reinterpret_cast<float*>(G.out[k] + (size_t)ly * A.out_stride + lx);
+                o[comp] = val;
+                if (comp == 0) o[3] = valid ? 1.0f : 0.0f;
+            }
+        }
+    }
+    flush(counters, cnt_depth_truncated, truncated);
+}
+
 // ---- level 0's shadow rays and shading in one persistent grid ----
 #if !defined(YRT_SHADOW_SHADE_FUSE)  // (its non-default build is the `unfused` library of tools/build_variants.py)
 // one level, 1 / 4 / 16 / 64 spp, at most 32 lights: an item of the any-hit grid (a 64-sample
@@ -2754,6 +3006,12 @@ __global__ __launch_bounds__(WF_BLOCK) void k_accumulate_passes(dev_render_args 
     accumulate_plane(A, C, [&] { return k == pass_count ? B.rad : P.smp[k]; }, [&] { return P.out[k]; });
 }
 
+// the light groups' planes: blockIdx.y is the plane, its samples G.smp[k]
+__global__ __launch_bounds__(WF_BLOCK) void k_accumulate_groups(dev_render_args A, chunk_args C, group_buffers G) {
+    const int k = (int)blockIdx.y;
+    accumulate_plane(A, C, [&] { return G.smp[k]; }, [&] { return G.out[k]; });
+}
+
 size_t align_up(size_t x) { return (x + 255) & ~size_t(255); }
 
 // the per-level, per-segment mirror-ray counters (seg_counter)
@@ -2784,6 +3042,18 @@ size_t workspace_bytes(int cap, int spp, int nlights, int nlevels, int pass_plan
     b += 2 * align_up(4 * nt) + align_up(nt * camera_list_max * 32);
     // levels >= 1: ray_o, ray_d; levels < last: rec0, rec1 (one slab each)
     if (nlevels > 1) b += 4 * align_up((size_t)(nlevels - 1) * 16 * c);
+    return b;
+}
+
+// the light groups' share, behind yrt_render's workspace (the same with or without them): the
+// table of lights sorted by plane; per-sample values of nplanes - 1 planes (plane 0's are B.rad)
+// in the unfused and mirror shapes (smp_samples of them, else 0); mirror-level records of
+// nplanes - 1 planes (plane 0's are B.rec0_)
+size_t group_table_ints(int nlights) { return group_planes + 1 + 2 * (size_t)nlights; }
+size_t group_bytes(int cap, int nlights, int nlevels, int nplanes, size_t smp_samples) {
+    size_t b = align_up(sizeof(int) * group_table_ints(nlights));
+    if (smp_samples) b += (size_t)(nplanes - 1) * align_up(16 * smp_samples);
+    if (nlevels > 1) b += (size_t)(nplanes - 1) * align_up((size_t)(nlevels - 1) * 16 * (size_t)cap);
     return b;
 }
 
@@ -2912,9 +3182,11 @@ void launch_chunk_setup(const device_scene& ds, const wf_buffers& B, int nrec, c
 
 // passes: yrt_render_passes' planes (P.mask, P.out; out is then P.out[pass_count], the beauty,
 // or null), shaded by k_shade_passes and summed by k_accumulate_passes; null: yrt_render
+// groups: yrt_render_light_groups' planes (nplanes, amb_mask, out; ds.group_tab their table),
+// shaded by k_shade_groups and summed by k_accumulate_groups; not together with passes
 template <bool COUNT, bool PACKET, typename SE>
 hipError_t run(device_scene& ds, const dev_render_args& A, float4* out, unsigned long long* counters,
-               hipStream_t stream, const pass_buffers* passes = nullptr) {
+               hipStream_t stream, const pass_buffers* passes = nullptr, const group_buffers* groups = nullptr) {
     const int spp = A.samples * A.samples;
     const int tiles_x = (A.tile_w + TILE - 1) / TILE;
     const int tiles_y = (A.tile_h + TILE - 1) / TILE;
@@ -2942,7 +3214,8 @@ hipError_t run(device_scene& ds, const dev_render_args& A, float4* out, unsigned
     const int smp_planes = passes && !fuse ? __builtin_popcount(passes->mask & ((1u << pass_count) - 1)) : 0;
     auto bytes_of = [&](long long tgt) {
         const int pix = cap_for(tgt);
-        return workspace_bytes(cap_of(pix), spp, ds.nlights, nlevels, smp_planes, (size_t)pix * spp);
+        return workspace_bytes(cap_of(pix), spp, ds.nlights, nlevels, smp_planes, (size_t)pix * spp) +
+               (groups ? group_bytes(cap_of(pix), ds.nlights, nlevels, groups->nplanes, fuse ? 0 : (size_t)pix * spp) : 0);
     };
     const int pix_per_chunk = cap_for(chunk_target(ds, A, bytes_of));
     const int seg = seg_of(pix_per_chunk);
@@ -2951,7 +3224,9 @@ hipError_t run(device_scene& ds, const dev_render_args& A, float4* out, unsigned
     const item_magic M = make_item_magic(spp, A.samples, tiles_x, A.band, (uint64_t)npix_total,
                                          (uint64_t)pix_per_chunk * spp, (uint64_t)tiles_y * TILE, A.width, A.height,
                                          A.x0, A.y0);
-    const size_t need = workspace_bytes(cap, spp, ds.nlights, nlevels, smp_planes, (size_t)pix_per_chunk * spp);
+    const size_t group_smp = fuse ? 0 : (size_t)pix_per_chunk * spp;
+    const size_t need = workspace_bytes(cap, spp, ds.nlights, nlevels, smp_planes, (size_t)pix_per_chunk * spp) +
+                        (groups ? group_bytes(cap, ds.nlights, nlevels, groups->nplanes, group_smp) : 0);
     if (hipError_t e = grow_workspace(ds, need); e != hipSuccess) return e;
     wf_buffers B = carve(ds.work, cap, spp, ds.nlights, nlevels);
     B.trel = ds.trel;
@@ -2963,6 +3238,22 @@ hipError_t run(device_scene& ds, const dev_render_args& A, float4* out, unsigned
         char* at = (char*)ds.work + workspace_bytes(cap, spp, ds.nlights, nlevels);
         for (int k = 0; k < pass_count && smp_planes; k++)
             if (P.mask >> k & 1) P.smp[k] = (f4*)at, at += align_up(16 * (size_t)pix_per_chunk * spp);
+    }
+    group_buffers G = {};
+    if (groups) {
+        G = *groups;
+        char* at = (char*)ds.work + workspace_bytes(cap, spp, ds.nlights, nlevels);
+        // (the table's source, ds.group_tab, outlives the call; a copy from pageable memory is
+        // staged before hipMemcpyAsync returns)
+        if (hipError_t e = hipMemcpyAsync(at, ds.group_tab.data(), sizeof(int) * ds.group_tab.size(),
+                                          hipMemcpyHostToDevice, stream);
+            e != hipSuccess)
+            return e;
+        G.tab = (const int*)at, at += align_up(sizeof(int) * group_table_ints(ds.nlights));
+        G.smp[0] = B.rad, G.rec[0] = B.rec0_;
+        for (int k = 1; k < G.nplanes && group_smp; k++) G.smp[k] = (f4*)at, at += align_up(16 * group_smp);
+        for (int k = 1; k < G.nplanes && nlevels > 1; k++)
+            G.rec[k] = (f4*)at, at += align_up((size_t)(nlevels - 1) * 16 * (size_t)cap);
     }
     bool list_stats = false;
     ds.last_camera_lists = ds.last_bundles = false;
@@ -3005,7 +3296,7 @@ hipError_t run(device_scene& ds, const dev_render_args& A, float4* out, unsigned
         // ... which shades its items too (k_shadow_shade_persist: no occlusion bytes, no k_shade
         // launch) where an item is whole pixels and a lane's lights fit its mask
         const bool shadow_shade = YRT_SHADOW_SHADE_KERNEL && shadow_persist && !stage &&
-                                  nlevels == 1 && !passes && 64 % spp == 0 && ds.nlights <= 32;
+                                  nlevels == 1 && !passes && !groups && 64 % spp == 0 && ds.nlights <= 32;
         // ... and walk the bundles' candidate lists (k_bundle_lists) instead of the tree
         const bool bundles_possible = !stage && shadow_persist && bundle_lights(ds.nlights) > 0 &&
                                       ds.view.nwtop >= YRT_BUNDLE_MIN_TOP;
@@ -3139,7 +3430,23 @@ hipError_t run(device_scene& ds, const dev_render_args& A, float4* out, unsigned
             hipLaunchKernelGGL((k_shade_passes<FU, WF_BLOCK, false>), GRID, dim3(WF_BLOCK), 0, stream, ds.view, A,  \
                                level, nsamp, A.max_depth, B, P, counters, C);                                     \
     } while (0)
-            if (passes) {
+#define YRT_SHADE_GROUPS_LAUNCH(FU, GRID)                                                                          \
+    do {                                                                                                          \
+        if (occ4)                                                                                                 \
+            hipLaunchKernelGGL((k_shade_groups<FU, WF_BLOCK, true>), GRID, dim3(WF_BLOCK), 0, stream, ds.view, A, level, \
+                               nsamp, A.max_depth, B, G, counters, C);                                            \
+        else                                                                                                      \
+            hipLaunchKernelGGL((k_shade_groups<FU, WF_BLOCK, false>), GRID, dim3(WF_BLOCK), 0, stream, ds.view, A,  \
+                               level, nsamp, A.max_depth, B, G, counters, C);                                     \
+    } while (0)
+            if (groups) {
+                if constexpr (!COUNT) {  // (launch_render_wavefront_light_groups never counts work)
+                    if (fuse)
+                        YRT_SHADE_GROUPS_LAUNCH(true, dim3(grid));
+                    else
+                        YRT_SHADE_GROUPS_LAUNCH(false, dim3(level ? stride_grid : grid));
+                }
+            } else if (passes) {
                 if constexpr (!COUNT) {  // (launch_render_wavefront_passes never counts work)
                     if (fuse)
                         YRT_SHADE_PASSES_LAUNCH(true, dim3(grid));
@@ -3151,6 +3458,7 @@ hipError_t run(device_scene& ds, const dev_render_args& A, float4* out, unsigned
             } else {
                 YRT_SHADE_LAUNCH(false, WF_BLOCK, dim3(level ? stride_grid : grid));
             }
+#undef YRT_SHADE_GROUPS_LAUNCH
 #undef YRT_SHADE_PASSES_LAUNCH
 #undef YRT_SHADE_LAUNCH
             T.end(t, stream);
@@ -3160,7 +3468,10 @@ hipError_t run(device_scene& ds, const dev_render_args& A, float4* out, unsigned
         }
         if (!fuse) {
             t = T.begin(phase_accumulate, stream);
-            if (passes)
+            if (groups)
+                hipLaunchKernelGGL(k_accumulate_groups, dim3((C.npix + WF_BLOCK - 1) / WF_BLOCK, G.nplanes),
+                                   dim3(WF_BLOCK), 0, stream, A, C, G);
+            else if (passes)
                 hipLaunchKernelGGL(k_accumulate_passes, dim3((C.npix + WF_BLOCK - 1) / WF_BLOCK, pass_planes),
                                    dim3(WF_BLOCK), 0, stream, A, C, B, P);
             else
@@ -3321,6 +3632,39 @@ hipError_t launch_render_wavefront_passes(device_scene& ds, const dev_render_arg
     if (packet) return run<false, true, uint32_t>(ds, args, beauty, counters, stream, &P);
     if (ds.narrow_stack) return run<false, false, uint16_t>(ds, args, beauty, counters, stream, &P);
     return run<false, false, uint32_t>(ds, args, beauty, counters, stream, &P);
+}
+
+// The planes in the kernels' order: the groups, then the ambient plane and the beauty where
+// asked for. The table (group_buffers::tab): per plane the bounds of its lights, then the
+// lights sorted by plane, scene order inside a plane (the beauty's are all of them).
+hipError_t launch_render_wavefront_light_groups(device_scene& ds, const dev_render_args& args, const int* group_of,
+                                                int ngroups, const dev_light_group_planes& out,
+                                                unsigned long long* counters, bool packet, hipStream_t stream) {
+    if (args.tile_w <= 0 || args.tile_h <= 0) return clear_counters(counters, stream);  // (an empty window)
+    group_buffers G = {};
+    std::vector<int>& tab = ds.group_tab;
+    tab.assign(group_planes + 1, 0);
+    for (int g = 0; g < ngroups; g++) {
+        tab[G.nplanes] = (int)tab.size() - (group_planes + 1);
+        for (int li = 0; li < ds.nlights; li++)
+            if (group_of[li] == g) tab.push_back(li);
+        G.out[G.nplanes++] = (float4*)out.group[g];
+    }
+    if (out.ambient) {
+        tab[G.nplanes] = (int)tab.size() - (group_planes + 1);
+        G.amb_mask |= 1u << G.nplanes;
+        G.out[G.nplanes++] = (float4*)out.ambient;
+    }
+    if (out.beauty) {
+        tab[G.nplanes] = (int)tab.size() - (group_planes + 1);
+        for (int li = 0; li < ds.nlights; li++) tab.push_back(li);
+        G.amb_mask |= 1u << G.nplanes;
+        G.out[G.nplanes++] = (float4*)out.beauty;
+    }
+    for (int k = G.nplanes; k <= group_planes; k++) tab[k] = (int)tab.size() - (group_planes + 1);
+    if (packet) return run<false, true, uint32_t>(ds, args, nullptr, counters, stream, nullptr, &G);
+    if (ds.narrow_stack) return run<false, false, uint16_t>(ds, args, nullptr, counters, stream, nullptr, &G);
+    return run<false, false, uint32_t>(ds, args, nullptr, counters, stream, nullptr, &G);
 }
 
 }  // namespace yrt

@@ -82,6 +82,9 @@ struct device_scene {
     // yrt_scene_set_lds_staging: the persistent walks read the instance tree's top from LDS
     int lds_staging = 0;
     int last_lds_staging = 0;  // what the last render staged: bit 0 closest hit, bit 1 any hit
+    // yrt_render_light_groups: the last call's table of lights sorted by plane, the source of
+    // its copy to the device (wavefront.hip group_buffers::tab)
+    std::vector<int> group_tab;
     phase_timer timer;
 };
 
@@ -169,5 +172,20 @@ struct dev_pass_planes {
 hipError_t launch_render_wavefront_passes(device_scene& ds, const dev_render_args& args, unsigned mask,
                                           const dev_pass_planes& out, void* beauty_rgba, unsigned long long* counters,
                                           bool packet, hipStream_t stream);
+
+// light groups (wavefront.hip k_shade_groups / k_accumulate_groups): the planes of
+// yrt_render_light_groups, float4 per pixel in launch_render's layout. group_of (host memory,
+// copied during the call) gives each of the scene's lights its group in [-1, ngroups); the
+// first ngroups of out.group are written, and ambient and beauty where not null. One walk:
+// counters and timings as after launch_render_wavefront.
+constexpr int light_groups_max = 8;
+struct dev_light_group_planes {
+    float* group[light_groups_max];
+    float* ambient;
+    float* beauty;
+};
+hipError_t launch_render_wavefront_light_groups(device_scene& ds, const dev_render_args& args, const int* group_of,
+                                                int ngroups, const dev_light_group_planes& out,
+                                                unsigned long long* counters, bool packet, hipStream_t stream);
 
 }  // namespace yrt
