@@ -1049,6 +1049,308 @@ __device__ __forceinline__ bool packet_first(const dev_scene_view& S, const ray3
     return true;
 }
 
+// ---- the camera rays' list-mode closest hit as nested loops ----
+// packet_first<COUNT = false, REL, LIST> -- the one instantiation the flagship's primary grid
+// runs -- with the walk's levels written as loops inside one another instead of one flat loop
+// steered by level / lstep / descend / finished:
+//
+//   for each list entry (the tree's root as the one virtual entry of a wave without a list)
+//       instance-level walk of the entry, floor 0: descent on the camera-relative records,
+//       pops down to sp == 0
+//           at an instance-level leaf: for each kept instance, in slot order
+//               enter it; shape walk, floor = the sp at leaf entry: descent, leaf, pop
+//           the world ray back, once per leaf
+//
+// Every lane sees the same box, primitive and tmax operations on the same values in the same
+// order as in packet_first (the bodies are its bodies); what goes is the state the flat loop
+// sets and tests again at every transition. The floor is a loop invariant, the shape's record
+// base is a scalar of the instance loop, the instance entry stands once, and the octant is an
+// invariant of the loop around each descent (the dispatch stays in front of the descent: the
+// leaf code is not instantiated per octant). 0: k_primary_persist's list mode calls
+// packet_first as before (tools/build_variants.py "flatwalk").
+#if !defined(YRT_FIRST_NESTED)  // (its non-default build is the `flatwalk` library of tools/build_variants.py)
+#define YRT_FIRST_NESTED 1
+#endif
+#define YRT_OCT_DISPATCH(oct, X) \
+    switch (oct) {               \
+        case 0: X(0); break;     \
+        case 1: X(1); break;     \
+        case 2: X(2); break;     \
+        case 3: X(3); break;     \
+        case 4: X(4); break;     \
+        case 5: X(5); break;     \
+        case 6: X(6); break;     \
+        case 7: X(7); break;     \
+        default: X(8); break;    \
+    }
+template <int BS = packet_block>
+__device__ __forceinline__ bool packet_first_list(const dev_scene_view& S, const ray3& wray, bool valid,
+                                                  hit_record& hr, work_counts& wc, const f4* trel, const f4* lbase,
+                                                  int ln) {
+    static_assert(spine_len == 2, "packet_first_list walks two-node spine records");
+    constexpr bool SM = YRT_STACK_MASKS;  // the stack keeps lane masks (inner_pop_avail)
+    const unsigned long long live = ballot(valid && !is_nan(wray.tmin) && !is_nan(wray.tmax));
+    if (!live) return false;
+    // the one origin of the wave's rays, from the first live lane into SGPRs (packet_first, REL)
+    const int fl = __builtin_ctzll(live);
+    const vec3f wo = {__int_as_float(__builtin_amdgcn_readlane(__float_as_int(wray.o.x), fl)),
+                      __int_as_float(__builtin_amdgcn_readlane(__float_as_int(wray.o.y), fl)),
+                      __int_as_float(__builtin_amdgcn_readlane(__float_as_int(wray.o.z), fl))};
+    const vec3f wd = wray.d;
+    // tmin and tmax in registers of their own: the camera rays' are compile-time constants, and
+    // the walk built around the constants spills a VGPR in the caller's pixel arithmetic
+    float tmin = wray.tmin, tmax = wray.tmax;
+    asm volatile("" : "+v"(tmin), "+v"(tmax));
+    vec3f co = wo, cd = wd, ci = rcp3(wd, live);
+    // the world inverse direction, parked in LDS for the returns from instance leaves
+    __shared__ float wi_lds[3][BS];
+    // (the slot is the thread's own: threadIdx.x stays live in the persistent caller, so no wave
+    // index is held across the walk and no lane index is recomputed)
+    {
+        const int t = (int)threadIdx.x;
+        wi_lds[0][t] = ci.x, wi_lds[1][t] = ci.y, wi_lds[2][t] = ci.z;
+    }
+    float hw1 = 0, hw2 = 0;
+    int hslot = -1, hei = -1;
+    int stk_node = 0, stk_mlo = 0, stk_mhi = 0;
+    // alive: the walk's live lanes less the ones a NaN tmax took out (packet_first's
+    // live & ~done, kept as one mask)
+    unsigned long long alive = live, mask = 0;
+    int sp = 0, node = 0;
+    const int woct = wave_octant(ci, live);
+    // the instance-local direction of the instances with an identity rotation, once per walk
+    vec3f icd, ici;
+    enter_direction(frame3f{{1, 0, 0}, {0, 1, 0}, {0, 0, 1}, {0, 0, 0}}, wd, live, icd, ici);
+    const int ioct = wave_octant(ici, live);
+    // the list's address, length and next entry, parked in this wave's LDS slot between list
+    // steps (packet_first)
+    __shared__ int list_lds[BS / 64][4];
+    int* const lst = list_lds[threadIdx.x >> 6];
+    lst[0] = (int)(unsigned)(unsigned long long)lbase, lst[1] = (int)((unsigned long long)lbase >> 32);
+    lst[2] = ln, lst[3] = 0;
+    for (;;) {
+        // ---- list step: the next entry some live lane passes, or the end of the walk ----
+        uint32_t lcl = 0;  // a list entry that is a leaf: its count word (no descent in front of it)
+        mask = 0;
+        asm volatile("" ::: "memory");
+        const int lend = uniform(lst[2]);
+        int lnext = uniform(lst[3]);
+        if (lend < 0) {
+            if (lnext == 0) node = 0, mask = alive, lnext = 1;  // the root's record
+        } else {
+            const f4* lb = (const f4*)((unsigned long long)(unsigned)uniform(lst[1]) << 32 | (unsigned)uniform(lst[0]));
+            while (lnext < lend) {
+                float4 e[2];
+                ld_records_at<2>(lb, (unsigned)(2 * lnext), e);
+                lnext++;
+#ifdef YRT_WIDE_STATS
+                wc.tex++;  // (stats build: list entries tested)
+#endif
+                const unsigned long long lanes = alive;
+                unsigned long long m;
+#define YRT_LE(o) m = list_entry_test<o>(ci, tmin, tmax, e, lanes)
+                YRT_OCT_DISPATCH(woct, YRT_LE)
+#undef YRT_LE
+                if (m) {
+                    const int w0 = uniform(ibits(e[0].w));
+                    const uint32_t w1 = (uint32_t)uniform(ibits(e[1].w));
+                    mask = m;
+                    if (w1 & leaf_bit) {  // an instance-level leaf: its instances next
+                        node = w0, lcl = w1;
+                    } else {
+                        // a subtree root the lanes of m pass: its child start pushed for them,
+                        // on at child start+1 (packet_first)
+                        stk_node = writelane(stk_node, w0, sp);
+                        if constexpr (SM) {
+                            stk_mlo = writelane(stk_mlo, (int)(uint32_t)m, sp);
+                            stk_mhi = writelane(stk_mhi, (int)(uint32_t)(m >> 32), sp);
+                        }
+                        sp++;
+                        node = w0 + spine_record_bytes;
+                    }
+                    break;
+                }
+            }
+        }
+        if (!mask) break;
+        lst[3] = lnext;
+        asm volatile("" ::: "memory");
+        // ---- the instance-level walk of this entry: the world ray, floor 0 ----
+        for (;;) {
+            if (!(lcl & leaf_bit)) {
+                DBG_CHECK(node >= 0 && (node % spine_record_bytes) == 0 && sp >= 0 && sp < 63 &&
+                              node / spine_record_bytes < S.ntnodes,
+                          1, node, sp, 0, 0, 0);
+                // (without stack masks: the lanes a popped node is tested with, inner_pop_avail)
+                const unsigned long long pop_arg = SM ? ~alive : alive;
+#define YRT_FD(o)                                                                                            \
+    first_descend<o, false, true, 0, SM, true>(trel, co, ci, tmin, tmax, 0ull, node, mask, sp, stk_node, stk_mlo, \
+                                               stk_mhi, lcl, wc, 0, pop_arg, nullptr)
+                YRT_OCT_DISPATCH(woct, YRT_FD)
+#undef YRT_FD
+            }
+            if (mask) {
+                // ---- an instance-level leaf: its kept instances in slot order ----
+                unsigned long long avail = mask;  // the leaf's lanes, less the done ones
+                const int lstart = node, lcount = (int)(lcl & 0xffffu);
+                int inst_next = lstart, inst_end = lstart + lcount;
+                // a camera list's leaf: the runs of excluded instances at either end of it are
+                // dropped, once per leaf (packet_first; a tree leaf's bits are 0)
+                const uint32_t skip = (lcl >> 16) & 0x7fffu;
+                if (skip) {
+                    const uint32_t keep = ~skip & ((1u << lcount) - 1u);  // (count <= 15 when skip != 0)
+                    if (!keep) {
+                        inst_end = inst_next;
+                    } else {
+                        inst_next = lstart + __builtin_ctz(keep);
+                        inst_end = lstart + 32 - __builtin_clz(keep);
+                    }
+                }
+                const int base = sp;  // the shape walks' floor
+                // (no lane left: the remaining instances would be entered for nothing)
+                for (int k = inst_next; k < inst_end && avail; k++) {
+                    // enter instance k: transform_ray_inverse (vmath.h:275-278), every lane
+                    DBG_CHECK(k >= 0 && k < S.ninst, 3, k, inst_end, sp, base, 0);
+#ifdef YRT_WIDE_STATS
+                    wc.inst++;
+#endif
+                    float4 fr[4];
+                    ld_records_at<4>(S.tinst, (unsigned)(4 * k), fr);
+                    const frame3f f = {xyz(fr[0]), xyz(fr[1]), xyz(fr[2]), xyz(fr[3])};
+                    co = transform_point_inverse(f, wo);
+                    const bool ident = (uniform(ibits(fr[0].w)) & (int)inst_identity_bit) != 0;
+                    if (ident)
+                        cd = icd, ci = ici;
+                    else
+                        enter_direction(f, wd, alive, cd, ci);
+                    const uint32_t rk = (uint32_t)uniform(ibits(fr[3].w));
+                    // the shape's records: scalar for the whole shape walk
+                    unsigned long long sbits = (unsigned long long)(S.spair + spine_record_f4 * (rk & 0x3fffffffu));
+                    sbits = (unsigned long long)(uint32_t)uniform((int)(sbits >> 32)) << 32 |
+                            (uint32_t)uniform((int)(uint32_t)sbits);
+                    asm volatile("" : "+s"(sbits));
+                    const f4* const sbase = (const f4*)sbits;
+                    const int kind = (int)(rk >> 30);
+                    const int soct = ident ? ioct : wave_octant(ci, alive);
+                    node = 0;  // the shape root, tested like any popped node
+                    mask = avail;
+                    for (;;) {
+                        DBG_CHECK(node >= 0 && (node % spine_record_bytes) == 0 && sp >= 0 && sp < 63 &&
+                                      (int)((sbase - S.spair) / 4) + node / spine_record_bytes < S.nsnodes,
+                                  1, node, sp, 1, (int)((sbase - S.spair) / 4), base);
+                        const unsigned long long pop_arg = SM ? ~alive : avail;
+#define YRT_FD(o)                                                                                              \
+    first_descend<o, false, false, 0, SM, true>(sbase, co, ci, tmin, tmax, 0ull, node, mask, sp, stk_node, stk_mlo, \
+                                                stk_mhi, lcl, wc, base, pop_arg, nullptr)
+                        YRT_OCT_DISPATCH(soct, YRT_FD)
+#undef YRT_FD
+                        if (mask) {
+                            // ---- a shape leaf: its primitives in slot order ----
+                            const unsigned long long lmask = mask;
+                            const int pstart = node, pcount = (int)(lcl & 0xffffu);
+                            unsigned long long leaf_hits = 0;  // the lanes that hit a primitive of this leaf
+                            DBG_CHECK(pstart >= 0 && pstart + pcount <= S.nsprims, 2, pstart, pcount, 1, kind, sp);
+#ifdef YRT_WIDE_STATS
+                            wc.box++, wc.prim += (unsigned)pcount;  // (stats build: shape leaves, primitive tests)
+#endif
+                            if (kind == kind_triangles) {
+                                for (int i = pstart; i < pstart + pcount; i++) {
+                                    float4 pv[3];
+                                    ld_records_at<3>(S.sprims, (unsigned)(3 * i), pv);
+                                    float t, w1, w2;
+                                    const unsigned long long hm = tri_hit_mask<true>(
+                                        co, cd, tmin, tmax, xyz(pv[0]), xyz(pv[1]), xyz(pv[2]), t, w1, w2, lmask);
+                                    // most triangles hit no lane: their record-keeping selects are skipped
+                                    if (hm) {
+                                        const bool h = lane_in(hm);
+                                        tmax = h ? t : tmax;
+                                        hslot = h ? k : hslot;
+                                        hei = h ? ibits(pv[0].w) : hei;
+                                        hw1 = h ? w1 : hw1;
+                                        hw2 = h ? w2 : hw2;
+                                        leaf_hits |= hm;
+                                    }
+                                }
+                            } else {
+                                const bool in = lane_in(lmask);
+                                for (int i = pstart; i < pstart + pcount; i++) {
+                                    float4 pv[3];
+                                    ld_records_at<3>(S.sprims, (unsigned)(3 * i), pv);
+                                    // lines: ew = {1-s, s, 0, 0}; points: {1, 0, 0, 0} (packet_first)
+                                    float t;
+                                    vec4f ew;
+                                    const ray3 lr = {co, cd, tmin, tmax};
+                                    bool h = kind == kind_lines
+                                                 ? line_hit(lr, xyz(pv[0]), xyz(pv[1]), pv[1].w, pv[2].x, t, ew)
+                                                 : point_hit(lr, xyz(pv[0]), pv[1].x, t, ew);
+                                    h = h && in;
+                                    tmax = h ? t : tmax;
+                                    hslot = h ? k : hslot;
+                                    hei = h ? ibits(pv[0].w) : hei;
+                                    hw1 = h ? ew.y : hw1;
+                                    hw2 = h ? ew.z : hw2;
+                                    leaf_hits |= ballot(h);
+                                }
+                            }
+                            // a NaN tmax fails every later slab test: such a lane leaves the walk
+                            const unsigned long long out = leaf_hits & ballot(is_nan(tmax));
+                            alive &= ~out;
+                            avail &= ~out;
+                        }
+                        // ---- pop inside the shape, down to the leaf's floor ----
+                        if constexpr (SM) {
+                            if (!inner_pop(base, ~alive, node, mask, sp, stk_node, stk_mlo, stk_mhi)) break;
+                        } else {
+                            if (!avail) {  // no lane left: the shape's entries are all skipped
+                                sp = base;
+                                break;
+                            }
+                            if (!inner_pop_avail(base, avail, node, mask, sp, stk_node)) break;
+                        }
+                    }
+                }
+                // the world ray back, once per leaf
+                co = wo;
+                cd = wd;
+                {
+                    const int t = (int)threadIdx.x;
+                    ci = {wi_lds[0][t], wi_lds[1][t], wi_lds[2][t]};
+                }
+            }
+            lcl = 0;
+            // ---- pop at the instance level ----
+            if constexpr (SM) {
+                if (!inner_pop(0, ~alive, node, mask, sp, stk_node, stk_mlo, stk_mhi)) break;
+            } else {
+                if (!alive) {
+                    sp = 0;
+                    break;
+                }
+                if (!inner_pop_avail(0, alive, node, mask, sp, stk_node)) break;
+            }
+        }
+    }
+#ifdef YRT_WIDE_STATS
+    {
+        const unsigned long long hitl = ballot(hslot >= 0) & live;
+        if ((threadIdx.x & 63) == 0) {
+            unsigned long long* line = g_first_stats + 16 * ((blockIdx.x * 7u + threadIdx.x / 64u) & 1023u);
+            const unsigned long long v[10] = {1, wc.tex, wc.wnode, wc.inst, wc.wprim, wc.box, wc.prim, 0,
+                                              (unsigned long long)__popcll(live), (unsigned long long)__popcll(hitl)};
+            for (int i = 0; i < 10; i++) atomicAdd(line + i, v[i]);
+        }
+        wc = work_counts{};  // (a persistent caller keeps one wc across its items)
+    }
+#endif
+    if (hslot < 0) return false;
+    hr.slot = hslot;
+    hr.ei = hei;
+    hr.ew = {1 - hw1 - hw2, hw1, hw2, 0};
+    hr.dist = tmax;
+    return true;
+}
+#undef YRT_OCT_DISPATCH
+
 // A wide record through the scalar cache: its first 112 bytes (bounds and child words:
 // x16 + x8 + x4, 28 SGPRs instead of 32) -- the slot count in the last row is implied by
 // the child words, an empty slot's word being wide_leaf exactly (a leaf of no

@@ -581,7 +581,8 @@ __device__ __forceinline__ void store_item_box(const wf_buffers& B, int idx, boo
 
 // ---- level 0: camera rays + closest hit + surface ----
 // the camera samples idx of one wave: eval_camera, closest hit, surface record
-template <bool COUNT, bool PACKET, typename SE, int BS = packet_block, int LDSN = 0, bool LIST = false>
+template <bool COUNT, bool PACKET, typename SE, int BS = packet_block, int LDSN = 0, bool LIST = false,
+          bool NESTED = false>
 __device__ __forceinline__ bool primary_samples(const dev_scene_view& S, const dev_render_args& A, const chunk_args& C,
                                                 const wf_buffers& B, tracer<false, COUNT, PACKET, SE, BS>& T, int idx,
                                                 work_counts& wc, const float4* lds = nullptr) {
@@ -665,7 +666,11 @@ __device__ __forceinline__ bool primary_samples(const dev_scene_view& S, const d
                 lbase = B.clist + (size_t)t0 * camera_list_max * 2;
             }
         }
-        hit = packet_first<COUNT, BS, true, LDSN, LIST>(S, ray, valid, hr, wc, B.trel, lds, lbase, ln);
+        // the list mode's walk as nested loops (packet_first_list; YRT_FIRST_NESTED=0: the flat one)
+        if constexpr (NESTED && LIST && !COUNT && LDSN == 0)
+            hit = packet_first_list<BS>(S, ray, valid, hr, wc, B.trel, lbase, ln);
+        else
+            hit = packet_first<COUNT, BS, true, LDSN, LIST>(S, ray, valid, hr, wc, B.trel, lds, lbase, ln);
     } else {
         hit = T.trace(S, ray, valid, hr, wc);
     }
@@ -918,7 +923,7 @@ __global__ __launch_bounds__(YRT_PRIMARY_SP_BLOCK, YRT_PRIMARY_WAVES) void k_pri
 #endif
         asm volatile("" ::: "memory");
         // (lane_now(), not `lane`: a lane index held across the walk would be spilled)
-        const bool valid = primary_samples<false, true, SE, SPB, LDSN, LIST>(S, A_lds, C_lds, B_lds, T,
+        const bool valid = primary_samples<false, true, SE, SPB, LDSN, LIST, YRT_FIRST_NESTED != 0>(S, A_lds, C_lds, B_lds, T,
                                                                             (int)(it * 64) + lane_now(), wc, lds_rec);
         valid_n += (unsigned)__popcll(ballot(valid));
     }
