@@ -384,6 +384,48 @@ typedef struct yrt_light_group_planes {
 int yrt_render_light_groups(yrt_scene* ds, const yrt_render_params* p, const int* group_of, int nlights,
                             int ngroups, const yrt_light_group_planes* out, int mem, void* stream);
 
+/* ---- ID mattes: ranked id/coverage pairs per pixel, from one pass ----
+ * YRT_AOV_IDS is the pixel's first sample, so a mask cut from it is aliased at every
+ * silhouette. A matte stores, per pixel, the few ids that cover it, each with its share of the
+ * pixel's s*s camera samples: the matte of any set of ids is then a sum of coverages, box
+ * filtered exactly as the beauty is. A matte is computed per key; a key's value for a hit is
+ * the .x (INSTANCE: the instance index in scene order), .z (MATERIAL) or .w (SHAPE) of
+ * YRT_AOV_IDS. R = 4 * layers ranks are stored. Per pixel and key, over the beauty's sample
+ * grid (raytrace.cpp:228-250, jj outer, ii inner, each sample answered by intersect_first):
+ * start with an empty table of R entries; a sample that misses does nothing; a sample that hits
+ * with id v adds one to v's count if v is in the table, else appends (v, 1) if an entry is
+ * free, else is dropped and counted in the key's dropped total. After the last sample the
+ * entries are ordered by count descending, ties by id ascending; rank r is
+ * {id, float(count) / float(s*s)}, an unused rank {-1, +0.0f}. So per pixel of the image
+ * sum(counts) + the pixel's dropped samples == its hits; the misses' share is implicit.
+ * Local rows past the image edge read as id -1 and coverage 0. */
+enum { YRT_MATTE_INSTANCE = 0, YRT_MATTE_MATERIAL = 1, YRT_MATTE_SHAPE = 2, YRT_MATTE_KEY_COUNT = 3 };
+#define YRT_MATTE_LAYERS_MAX 2
+typedef struct yrt_matte_planes {          /* each plane 16 B per pixel, yrt_render's layout */
+    int*   ids[YRT_MATTE_KEY_COUNT][YRT_MATTE_LAYERS_MAX];       /* int4: ranks 4l .. 4l+3 */
+    float* coverage[YRT_MATTE_KEY_COUNT][YRT_MATTE_LAYERS_MAX];  /* float4, same ranks */
+} yrt_matte_planes;
+/* key_mask: bit 1 << YRT_MATTE_x per requested key, one to all three; layers: 1 or 2. Only the
+ * planes of the requested keys' first `layers` layers are read from `out` and written. Every
+ * key comes from the same walk. The fields of `p` are used and ignored exactly as in
+ * yrt_render_aovs (resolution, width, samples, camera, the window, the band interleave and
+ * out_stride are used); padding columns keep the caller's bytes; an empty window or band writes
+ * nothing and counts nothing. Host planes make the call synchronous, device planes are
+ * stream-ordered. yrt_last_stats then reports rays == camera_samples == window pixels * s*s,
+ * whatever the number of keys. A null handle, p or out, a key_mask that is 0 or has bits beyond
+ * the three keys, layers outside 1..2, a null plane among those requested, a bad `mem` or a bad
+ * camera index return YRT_ERR_INVALID_ARG before any device call. The pass shares no state with
+ * yrt_render. */
+int yrt_render_mattes(yrt_scene* ds, const yrt_render_params* p, unsigned key_mask, int layers,
+                      const yrt_matte_planes* out, int mem, void* stream);
+/* the dropped samples per key of the last yrt_render_mattes on the handle, summed over its
+ * window (0 for a key that was not requested, and before any such call); synchronises the stream */
+int yrt_scene_matte_dropped(yrt_scene* ds, unsigned long long dropped[YRT_MATTE_KEY_COUNT]);
+/* each instance's shape and material index, in scene order: what turns a material or shape id
+ * back into a set of instances. n is always set to their count; shape and material may each be
+ * NULL (both NULL: the count only), else the first min(n, cap) entries are written */
+int yrt_host_scene_instances(const yrt_host_scene* hs, int* shape, int* material, int cap, int* n);
+
 #ifdef __cplusplus
 }
 #endif

@@ -24,7 +24,7 @@ from ._native import RenderParams, Stats, YrtError, check
 
 __all__ = [
     "Scene", "DeviceScene", "load_scene", "build_bvh", "raytrace", "render_aovs", "render_passes", "render_light_groups",
-    "intersect_first",
+    "render_mattes", "matte", "intersect_first",
     "intersect_any", "shade_rays", "tonemap", "save_hdr_or_ldr", "render_params", "device_count", "YrtError",
 ]
 
@@ -144,6 +144,15 @@ class Scene:
         check(N.lib.yrt_host_scene_lights(self._h, inst, n.value, C.byref(n)), "yrt_host_scene_lights")
         return list(inst[:n.value])
 
+    def instances(self) -> list:
+        """(shape, material) of each instance, in scene order: what turns a material or shape
+        id of a matte (render_mattes) back into a set of instances"""
+        n = C.c_int()
+        check(N.lib.yrt_host_scene_instances(self._h, None, None, 0, C.byref(n)), "yrt_host_scene_instances")
+        shp, mat = (C.c_int * max(n.value, 1))(), (C.c_int * max(n.value, 1))()
+        check(N.lib.yrt_host_scene_instances(self._h, shp, mat, n.value, C.byref(n)), "yrt_host_scene_instances")
+        return list(zip(shp[:n.value], mat[:n.value]))
+
     def image_size(self, resolution: int, camera: int = 0):
         w, h = C.c_int(), C.c_int()
         check(N.lib.yrt_host_image_size(self._h, camera, resolution, C.byref(w), C.byref(h)),
@@ -245,6 +254,31 @@ class DeviceScene:
         mem = N.YRT_MEM_DEVICE if device_memory else N.YRT_MEM_HOST
         check(N.lib.yrt_render_aovs(self._h, C.byref(params), mask, C.byref(ap), mem, C.c_void_p(stream or 0)),
               "yrt_render_aovs")
+
+    def render_mattes_into(self, params: RenderParams, planes: dict, layers: int, device_memory: bool = True,
+                           stream: Optional[int] = None) -> None:
+        """Launch the ID-matte pass (yrt_render_mattes) into caller planes {key: {"ids": [pointer
+        per layer], "coverage": [pointer per layer]}}, 16 bytes per pixel each in render_into's
+        layout (int32 x 4 and float32 x 4: ranks 4 * layer .. 4 * layer + 3); only the named keys
+        are computed, all from one walk."""
+        mask, mp = _matte_mask(planes), N.MattePlanes()
+        for key, kp in planes.items():
+            for what, dst in (("ids", mp.ids), ("coverage", mp.coverage)):
+                ptrs = list(kp[what])
+                if len(ptrs) > N.YRT_MATTE_LAYERS_MAX:
+                    raise ValueError(f"at most {N.YRT_MATTE_LAYERS_MAX} layers per matte key")
+                for l, ptr in enumerate(ptrs):
+                    dst[N.MATTE_KEYS[key]][l] = ptr
+        mem = N.YRT_MEM_DEVICE if device_memory else N.YRT_MEM_HOST
+        check(N.lib.yrt_render_mattes(self._h, C.byref(params), mask, int(layers), C.byref(mp), mem,
+                                      C.c_void_p(stream or 0)), "yrt_render_mattes")
+
+    def matte_dropped(self) -> dict:
+        """the samples the last render_mattes_into dropped per key (their id found the key's
+        table full), 0 for a key it did not compute; waits for that pass"""
+        d = (C.c_ulonglong * N.YRT_MATTE_KEY_COUNT)()
+        check(N.lib.yrt_scene_matte_dropped(self._h, d), "yrt_scene_matte_dropped")
+        return {key: int(d[k]) for key, k in N.MATTE_KEYS.items()}
 
     def render_passes_into(self, params: RenderParams, planes: dict, beauty_ptr: Optional[int] = None,
                            device_memory: bool = True, stream: Optional[int] = None) -> None:
@@ -461,6 +495,64 @@ def render_aovs(scn, resolution: int = 720, samples: int = 1, *, aovs: Sequence[
     out = {n: np.zeros((h, w, 4), np.int32 if n == "ids" else np.float32) for n in aovs}
     ds.render_aovs_into(p, {n: a.ctypes.data for n, a in out.items()}, device_memory=False)
     return out
+
+
+def _matte_mask(names) -> int:
+    """the YRT_MATTE_* bit mask of key names; an unknown name raises before any native call"""
+    names = list(names)
+    bad = [n for n in names if n not in N.MATTE_KEYS]
+    if bad or not names:
+        raise ValueError((f"unknown matte key {bad[0]!r}" if bad else "no matte key named") +
+                         f" (one of {', '.join(N.MATTE_KEYS)})")
+    mask = 0
+    for n in names:
+        mask |= 1 << N.MATTE_KEYS[n]
+    return mask
+
+
+def render_mattes(scn, resolution: int = 720, samples: int = 1, *, keys: Sequence[str] = ("instance",),
+                  ranks: int = 4, width: int = 0, window=None, camera: int = 0, device: int = 0) -> dict:
+    """ID mattes on raytrace's sample grid, every key from one pass: {key: {"ids": (H, W, ranks)
+    int32, "coverage": (H, W, ranks) float32}, ..., "dropped": {key: int}} for the keys
+    "instance", "material" and "shape" (the .x, .z and .w of render_aovs' "ids"). Per pixel the
+    ids covering it, ranked by their share of the pixel's s*s samples (ties by id), -1 and +0
+    in unused ranks; `ranks` is 4 or 8, and a sample whose id finds all ranks taken is dropped
+    and counted under "dropped". matte() turns a key's arrays and a set of ids into a mask that
+    is box filtered as the beauty is. `scn` is a Scene or a DeviceScene, as for raytrace."""
+    keys = list(keys)
+    _matte_mask(keys)
+    if isinstance(ranks, bool) or ranks not in (4, 8):
+        raise ValueError(f"ranks must be 4 or 8, not {ranks!r}")
+    layers = int(ranks) // 4
+    ds = _device_scene(scn, device)
+    p = render_params(resolution=resolution, samples=samples, width=width, camera=camera, window=window)
+    W, H = ds.image_size(p)
+    if window is None:
+        w, h = W, H
+    else:
+        w, h = window[2] or W - window[0], window[3] or H - window[1]
+    planes = {k: {"ids": [np.zeros((h, w, 4), np.int32) for _ in range(layers)],
+                  "coverage": [np.zeros((h, w, 4), np.float32) for _ in range(layers)]} for k in keys}
+    ds.render_mattes_into(p, {k: {n: [a.ctypes.data for a in v] for n, v in kp.items()} for k, kp in planes.items()},
+                          layers, device_memory=False)
+    out = {k: {n: np.concatenate(v, axis=-1) for n, v in kp.items()} for k, kp in planes.items()}
+    dropped = ds.matte_dropped()
+    out["dropped"] = {k: dropped[k] for k in keys}
+    return out
+
+
+def matte(m: dict, ids) -> np.ndarray:
+    """The (H, W) float32 matte of the ids in `ids` from one key's arrays m = {"ids", "coverage"}
+    (render_mattes): from +0, in rank order, acc = acc + where(m["ids"][..., r] in ids,
+    m["coverage"][..., r], +0) in float32 -- a fixed order, so the same bits every time."""
+    mi, mc = np.asarray(m["ids"]), np.asarray(m["coverage"], np.float32)
+    if mi.shape != mc.shape or mi.ndim < 1:
+        raise ValueError("matte: ids and coverage must have the same shape (..., ranks)")
+    wanted = np.asarray(list(ids), np.int64).reshape(-1)
+    acc = np.zeros(mi.shape[:-1], np.float32)
+    for r in range(mi.shape[-1]):
+        acc = (acc + np.where(np.isin(mi[..., r], wanted), mc[..., r], np.float32(0))).astype(np.float32)
+    return acc
 
 
 def _pass_mask(names) -> int:

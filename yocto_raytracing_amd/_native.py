@@ -114,6 +114,18 @@ class LightGroupPlanes(C.Structure):
     _fields_ = [("group", C.c_void_p * YRT_LIGHT_GROUPS_MAX), ("ambient", C.c_void_p), ("beauty", C.c_void_p)]
 
 
+# YRT_MATTE_*: key name -> index (bit of the key mask); per key and layer an int4 plane of ids
+# and a float4 plane of coverages, ranks 4 * layer .. 4 * layer + 3
+MATTE_KEYS = {"instance": 0, "material": 1, "shape": 2}
+YRT_MATTE_KEY_COUNT = 3
+YRT_MATTE_LAYERS_MAX = 2
+
+
+class MattePlanes(C.Structure):
+    _fields_ = [("ids", C.c_void_p * YRT_MATTE_LAYERS_MAX * YRT_MATTE_KEY_COUNT),
+                ("coverage", C.c_void_p * YRT_MATTE_LAYERS_MAX * YRT_MATTE_KEY_COUNT)]
+
+
 _vp = C.c_void_p
 _ip =C.POINTER(C.c_int)
 _sig = {
@@ -167,6 +179,10 @@ _sig = {
     "yrt_host_scene_lights": (C.c_int, [_vp, _ip, C.c_int, _ip]),
     "yrt_render_light_groups": (C.c_int, [_vp, C.POINTER(RenderParams), _ip, C.c_int, C.c_int,
                                           C.POINTER(LightGroupPlanes), C.c_int, _vp]),
+    "yrt_render_mattes": (C.c_int, [_vp, C.POINTER(RenderParams), C.c_uint, C.c_int, C.POINTER(MattePlanes), C.c_int,
+                                    _vp]),
+    "yrt_scene_matte_dropped": (C.c_int, [_vp, C.POINTER(C.c_ulonglong)]),
+    "yrt_host_scene_instances": (C.c_int, [_vp, _ip, _ip, C.c_int, _ip]),
 }
 EXPORTS = tuple(_sig)
 

@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "../../include/yrt.h"
+#include "matte_args.h"
 #include "yrt_render.h"
 
 struct yrt_host_scene {
@@ -26,6 +27,8 @@ struct yrt_scene {
     size_t scratch_bytes = 0;
     hipStream_t last_stream = nullptr;
     int trace_algorithm = YRT_ALGO_WAVEFRONT;  // walks used by yrt_trace_first/any
+    // yrt_render_mattes' dropped totals (device, yrt::matte_drop_slots lines), made by its first call
+    unsigned long long* matte_dropped = nullptr;
 };
 
 namespace {
@@ -263,6 +266,17 @@ int yrt_host_scene_lights(const yrt_host_scene* hs, int* inst, int cap, int* n) 
     return YRT_OK;
 }
 
+int yrt_host_scene_instances(const yrt_host_scene* hs, int* shape, int* material, int cap, int* n) {
+    if (!hs || !n || ((shape || material) && cap < 0)) return YRT_ERR_INVALID_ARG;
+    const auto& s = hs->scn;
+    for (size_t k = 0; k < s.instances.size() && (int)k < cap; k++) {
+        if (shape) shape[k] = s.instances[k].shp;
+        if (material) material[k] = s.instances[k].mat;
+    }
+    *n = (int)s.instances.size();
+    return YRT_OK;
+}
+
 int yrt_host_image_size(const yrt_host_scene* hs, int camera, int resolution, int* w, int* h) {
     if (!hs || !w || !h || camera < 0 || camera >= (int)hs->scn.cameras.size() || resolution <= 0)
         return YRT_ERR_INVALID_ARG;
@@ -468,6 +482,7 @@ void yrt_scene_free(yrt_scene* s) {
     if (s->ds) (void)hipSetDevice(s->ds->device);
     if (s->counters) (void)hipFree(s->counters);
     if (s->scratch) (void)hipFree(s->scratch);
+    if (s->matte_dropped) (void)hipFree(s->matte_dropped);
     yrt::device_scene_destroy(s->ds);
     delete s;
 }
@@ -610,6 +625,101 @@ int yrt_render_aovs(yrt_scene* s, const yrt_render_params* p, unsigned mask, con
         const hipError_t e2 = hipStreamSynchronize(st);
         hip_check(e, "aov render");
         hip_check(e2, "hipStreamSynchronize");
+        return YRT_OK;
+    });
+}
+
+static_assert(YRT_MATTE_KEY_COUNT == yrt::matte_key_count && YRT_MATTE_INSTANCE == yrt::matte_instance &&
+                  YRT_MATTE_MATERIAL == yrt::matte_material && YRT_MATTE_SHAPE == yrt::matte_shape &&
+                  YRT_MATTE_LAYERS_MAX == yrt::matte_layers_max,
+              "the kernel's key order and layer count are the header's");
+
+int yrt_render_mattes(yrt_scene* s, const yrt_render_params* p, unsigned key_mask, int layers,
+                      const yrt_matte_planes* out, int mem, void* stream) {
+    if (!s || !p || !out) return YRT_ERR_INVALID_ARG;
+    return guarded([&] {
+        if (const char* bad = yrt::matte_args_error(key_mask, layers, out, mem)) throw std::invalid_argument(bad);
+        auto r = resolve(*s->ds, *p);
+        if ((p->out_stride > 0 ? p->out_stride : r.tw) < r.tw)
+            throw std::invalid_argument("out_stride smaller than the window width");
+        hipStream_t st = (hipStream_t)stream;
+        hip_check(hipSetDevice(s->ds->device), "hipSetDevice");
+        yrt::dev_render_args a = {};
+        a.cam = yrt::make_dev_camera(s->ds->cameras[p->camera]);
+        a.width = r.W;
+        a.height = r.H;
+        a.samples = p->samples;
+        a.x0 = r.x0;
+        a.tile_w = r.tw;
+        a.y0 = r.y0;
+        a.tile_h = r.th;
+        a.band = p->band;
+        a.band_stride = p->band_stride;
+        a.band_offset = p->band_offset;
+        a.out_stride = p->out_stride > 0 ? p->out_stride : r.tw;
+        const size_t drop_bytes = (size_t)yrt::matte_drop_slots * yrt::matte_drop_stride * sizeof(unsigned long long);
+        if (!s->matte_dropped) hip_check(hipMalloc(&s->matte_dropped, drop_bytes), "hipMalloc(matte dropped totals)");
+        // the counters and the dropped totals are zeroed whatever the window: an empty one (a
+        // band offset without bands) launches nothing, and must not report the call before
+        hip_check(hipMemsetAsync(s->counters, 0, yrt::cnt_slots * yrt::cnt_count * sizeof(unsigned long long), st),
+                  "hipMemsetAsync");
+        hip_check(hipMemsetAsync(s->matte_dropped, 0, drop_bytes, st), "hipMemsetAsync");
+        s->last_stream = st;
+        if (r.tw <= 0 || r.th <= 0) return YRT_OK;
+        yrt::dev_matte_planes dp = {};
+        if (mem == YRT_MEM_DEVICE) {
+            for (int k = 0; k < YRT_MATTE_KEY_COUNT; k++)
+                for (int l = 0; l < layers; l++)
+                    if (key_mask >> k & 1) dp.ids[k][l] = out->ids[k][l], dp.coverage[k][l] = out->coverage[k][l];
+            hip_check(yrt::launch_mattes(*s->ds, a, key_mask, layers, dp, s->matte_dropped, s->counters, st),
+                      "matte kernel launch");
+            return YRT_OK;
+        }
+        // host planes: device staging of their own (the handle's scratch stays yrt_render's),
+        // copied back and released
+        const size_t bytes = (size_t)a.out_stride * r.th * 16;
+        const yrt::matte_staging lay = yrt::matte_stage_layout(key_mask, layers, *out, bytes);
+        struct staging {
+            void* p = nullptr;
+            ~staging() {
+                if (p) (void)hipFree(p);
+            }
+        } stage;
+        hip_check(hipMalloc(&stage.p, lay.bytes), "hipMalloc(matte staging)");
+        for (int k = 0; k < lay.count; k++) {
+            const auto& it = lay.items[k];
+            (it.coverage ? dp.coverage : dp.ids)[it.key][it.layer] = (char*)stage.p + it.offset;
+        }
+        // padding columns (out_stride > tile_w) keep the caller's bytes: they are staged too
+        if (a.out_stride > r.tw)
+            for (int k = 0; k < lay.count; k++)
+                hip_check(hipMemcpyAsync((char*)stage.p + lay.items[k].offset, lay.items[k].host, bytes,
+                                         hipMemcpyHostToDevice, st),
+                          "hipMemcpyAsync");
+        hipError_t e = yrt::launch_mattes(*s->ds, a, key_mask, layers, dp, s->matte_dropped, s->counters, st);
+        for (int k = 0; k < lay.count && e == hipSuccess; k++)
+            e = hipMemcpyAsync(lay.items[k].host, (char*)stage.p + lay.items[k].offset, bytes, hipMemcpyDeviceToHost, st);
+        // the staging is released only after the stream has drained, also on an error
+        const hipError_t e2 = hipStreamSynchronize(st);
+        hip_check(e, "matte render");
+        hip_check(e2, "hipStreamSynchronize");
+        return YRT_OK;
+    });
+}
+
+int yrt_scene_matte_dropped(yrt_scene* s, unsigned long long* dropped) {
+    if (!s || !dropped) return YRT_ERR_INVALID_ARG;
+    return guarded([&] {
+        for (int k = 0; k < YRT_MATTE_KEY_COUNT; k++) dropped[k] = 0;
+        if (!s->matte_dropped) return YRT_OK;  // no matte pass on this handle yet
+        std::vector<unsigned long long> lines((size_t)yrt::matte_drop_slots * yrt::matte_drop_stride);
+        hip_check(hipSetDevice(s->ds->device), "hipSetDevice");
+        hip_check(hipStreamSynchronize(s->last_stream), "hipStreamSynchronize");
+        hip_check(hipMemcpy(lines.data(), s->matte_dropped, lines.size() * sizeof(unsigned long long),
+                            hipMemcpyDeviceToHost),
+                  "hipMemcpy(matte dropped totals)");
+        for (int l = 0; l < yrt::matte_drop_slots; l++)
+            for (int k = 0; k < YRT_MATTE_KEY_COUNT; k++) dropped[k] += lines[(size_t)l * yrt::matte_drop_stride + k];
         return YRT_OK;
     });
 }

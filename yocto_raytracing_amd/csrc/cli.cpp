@@ -8,7 +8,9 @@
 // wavefront|megakernel|wavefront_lane, --time (print GPU time and Mrays/s), --aov LIST
 // (the camera hit's geometry buffers as .npy files beside the image), --passes LIST (the
 // image's lighting split, from the same render, as .npy files beside it), --light-groups LIST
-// (one plane per group of lights and the ambient plane, from the same render, as .npy files).
+// (one plane per group of lights and the ambient plane, from the same render, as .npy files),
+// --mattes LIST with --matte-ranks 4|8 (ID mattes: per key the ranked ids covering each pixel and
+// their coverages, from one pass, as .npy files).
 #include <algorithm>
 #include <chrono>
 #include <cstdio>
@@ -43,7 +45,13 @@ namespace {
             "  --light-groups LIST  one entry per light of the scene, in scene order: its group, 0 to 7, or -1\n"
             "                       for none, e.g. 0,1,0,-1,2; also write OUT.group<g>.npy per group (the image\n"
             "                       its lights alone produce) and OUT.ambient.npy, (H, W, 4) float32, from the\n"
-            "                       image's own render (one GPU, a wavefront algorithm)\n");
+            "                       image's own render (one GPU, a wavefront algorithm)\n"
+            "  --mattes LIST        also write OUT.matte_<key>.ids.npy, (H, W, ranks) int32, and\n"
+            "                       OUT.matte_<key>.coverage.npy, (H, W, ranks) float32, for each key of\n"
+            "                       instance,material,shape: per pixel the ids covering it, ranked by their\n"
+            "                       share of the pixel's samples (-1 and 0 in unused ranks), from one pass\n"
+            "                       (one GPU)\n"
+            "  --matte-ranks N      ranks per pixel and key of --mattes, 4 or 8 [4]\n");
     exit(msg ? 1 : 0);
 }
 
@@ -66,6 +74,24 @@ unsigned parse_aovs(const std::string& list) {
         int k = 0;
         while (k < YRT_AOV_COUNT && name != aov_names[k]) k++;
         if (k == YRT_AOV_COUNT) usage(("unknown --aov " + name).c_str());
+        mask |= 1u << k;
+        at = end + 1;
+    }
+    return mask;
+}
+
+const char* const matte_names[YRT_MATTE_KEY_COUNT] = {"instance", "material", "shape"};
+
+// --mattes' comma-separated key names as the YRT_MATTE_* bit mask
+unsigned parse_mattes(const std::string& list) {
+    unsigned mask = 0;
+    for (size_t at = 0; at <= list.size();) {
+        size_t end = list.find(',', at);
+        if (end == std::string::npos) end = list.size();
+        const std::string name = list.substr(at, end - at);
+        int k = 0;
+        while (k < YRT_MATTE_KEY_COUNT && name != matte_names[k]) k++;
+        if (k == YRT_MATTE_KEY_COUNT) usage(("unknown --mattes " + name).c_str());
         mask |= 1u << k;
         at = end + 1;
     }
@@ -108,18 +134,18 @@ std::vector<int> parse_light_groups(const std::string& list) {
     return groups;
 }
 
-// a (h, w, 4) array of 4-byte elements as a NumPy format 1.0 file, C order: the magic, the
-// version, the header dict's length, the dict padded with spaces so that the data starts on
+// a (h, w, channels) array of 4-byte elements as a NumPy format 1.0 file, C order: the magic,
+// the version, the header dict's length, the dict padded with spaces so that the data starts on
 // a multiple of 64 bytes, a newline, the data
-void save_npy(const std::string& path, const void* data, int w, int h, const char* descr) {
+void save_npy(const std::string& path, const void* data, int w, int h, const char* descr, int channels = 4) {
     std::string dict = std::string("{'descr': '") + descr + "', 'fortran_order': False, 'shape': (" +
-                       std::to_string(h) + ", " + std::to_string(w) + ", 4), }";
+                       std::to_string(h) + ", " + std::to_string(w) + ", " + std::to_string(channels) + "), }";
     while ((10 + dict.size() + 1) % 64) dict += ' ';
     dict += '\n';
     const unsigned char head[10] = {0x93, 'N', 'U', 'M', 'P', 'Y', 1, 0, (unsigned char)(dict.size() & 0xff),
                                     (unsigned char)(dict.size() >> 8)};
     FILE* f = fopen(path.c_str(), "wb");
-    const size_t bytes = (size_t)w * h * 16;
+    const size_t bytes = (size_t)w * h * 4 * channels;
     const bool ok = f && fwrite(head, 1, sizeof head, f) == sizeof head &&
                     fwrite(dict.data(), 1, dict.size(), f) == dict.size() && fwrite(data, 1, bytes, f) == bytes;
     if ((f && fclose(f) != 0) || !ok) throw yrt_cpp::error(YRT_ERR_IO, "cannot write " + path);
@@ -131,7 +157,8 @@ int main(int argc, char** argv) {
     int resolution = 720, samples = 1, device = 0, gpus = 1, width = 0, max_depth = 16, algorithm = YRT_ALGO_WAVEFRONT;
     float amb = 0.1f;
     bool timing = false;
-    unsigned aovs = 0, passes = 0;
+    unsigned aovs = 0, passes = 0, mattes = 0;
+    int matte_ranks = 4;
     std::vector<int> light_groups;
     bool groups = false;
     std::string out = "out.png", scenein;
@@ -158,6 +185,8 @@ int main(int argc, char** argv) {
         } else if (a == "--time") timing = true;
         else if (a == "--aov") aovs = parse_aovs(val());
         else if (a == "--passes") passes = parse_passes(val());
+        else if (a == "--mattes") mattes = parse_mattes(val());
+        else if (a == "--matte-ranks") matte_ranks = parse_int(val(), "--matte-ranks");
         else if (a == "--light-groups") light_groups = parse_light_groups(val()), groups = true;
         else if (a == "-h" || a == "--help") usage(nullptr);
         else if (!a.empty() && a[0] == '-') usage(("unknown option " + a).c_str());
@@ -167,6 +196,8 @@ int main(int argc, char** argv) {
     if (scenein.empty()) scenein = "scene.obj";  // the reference's default positional value
     if (gpus < 1) usage("--gpus must be >= 1");
     if (aovs && gpus > 1) usage("--aov renders on one GPU (--gpus 1)");
+    if (mattes && gpus > 1) usage("--mattes renders on one GPU (--gpus 1)");
+    if (matte_ranks != 4 && matte_ranks != 8) usage("--matte-ranks must be 4 or 8");
     if (passes && gpus > 1) usage("--passes renders on one GPU (--gpus 1)");
     if (passes && algorithm == YRT_ALGO_MEGAKERNEL) usage("--passes needs a wavefront algorithm, not --algorithm megakernel");
     if (groups && gpus > 1) usage("--light-groups renders on one GPU (--gpus 1)");
@@ -272,6 +303,45 @@ int main(int argc, char** argv) {
                 if (aovs >> k & 1)
                     save_npy(stem + "." + aov_names[k] + ".npy", planes[k].data(), hdr.width, hdr.height,
                              k == YRT_AOV_IDS ? "<i4" : "<f4");
+        }
+        if (mattes) {
+            // one pass for every requested key; a key's layers side by side in its two files
+            yrt_render_params p = scn->params;
+            p.resolution = resolution;
+            p.samples = samples;
+            const int layers = matte_ranks / 4;
+            const size_t npix = (size_t)hdr.width * hdr.height;
+            std::vector<std::vector<int>> ids(YRT_MATTE_KEY_COUNT * YRT_MATTE_LAYERS_MAX);
+            std::vector<std::vector<float>> cov(YRT_MATTE_KEY_COUNT * YRT_MATTE_LAYERS_MAX);
+            yrt_matte_planes mp = {};
+            for (int k = 0; k < YRT_MATTE_KEY_COUNT; k++)
+                for (int l = 0; l < layers; l++)
+                    if (mattes >> k & 1) {
+                        ids[k * YRT_MATTE_LAYERS_MAX + l].resize(npix * 4);
+                        cov[k * YRT_MATTE_LAYERS_MAX + l].resize(npix * 4);
+                        mp.ids[k][l] = ids[k * YRT_MATTE_LAYERS_MAX + l].data();
+                        mp.coverage[k][l] = cov[k * YRT_MATTE_LAYERS_MAX + l].data();
+                    }
+            yrt_cpp::check(yrt_render_mattes(scn->on_device(), &p, mattes, layers, &mp, YRT_MEM_HOST, nullptr),
+                           "render_mattes");
+            unsigned long long dropped[YRT_MATTE_KEY_COUNT] = {};
+            yrt_cpp::check(yrt_scene_matte_dropped(scn->on_device(), dropped), "matte_dropped");
+            std::vector<int> all_ids(npix * matte_ranks);
+            std::vector<float> all_cov(npix * matte_ranks);
+            for (int k = 0; k < YRT_MATTE_KEY_COUNT; k++) {
+                if (!(mattes >> k & 1)) continue;
+                for (size_t at = 0; at < npix; at++)
+                    for (int l = 0; l < layers; l++) {
+                        memcpy(&all_ids[at * matte_ranks + 4 * l], &ids[k * YRT_MATTE_LAYERS_MAX + l][at * 4], 16);
+                        memcpy(&all_cov[at * matte_ranks + 4 * l], &cov[k * YRT_MATTE_LAYERS_MAX + l][at * 4], 16);
+                    }
+                const std::string base = stem + ".matte_" + matte_names[k];
+                save_npy(base + ".ids.npy", all_ids.data(), hdr.width, hdr.height, "<i4", matte_ranks);
+                save_npy(base + ".coverage.npy", all_cov.data(), hdr.width, hdr.height, "<f4", matte_ranks);
+                if (dropped[k])
+                    fprintf(stderr, "matte %s: %llu samples dropped (more than %d ids in a pixel)\n", matte_names[k],
+                            dropped[k], matte_ranks);
+            }
         }
     } catch (const yrt_cpp::error& e) {
         fprintf(stderr, "%s\n", e.what());

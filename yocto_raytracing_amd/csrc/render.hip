@@ -381,3 +381,5 @@ hipError_t launch_tonemap(const float* rgba, int n, unsigned char* out, const to
 
 // the AOV pass (k_aov, launch_aovs): a file of its own in this translation unit
 #include "aov.hip"
+// the ID-matte pass (k_matte, launch_mattes), on the AOV pass's tile geometry
+#include "mattes.hip"

@@ -132,6 +132,25 @@ struct dev_aov_planes {
 hipError_t launch_aovs(const device_scene& ds, const dev_render_args& args, unsigned mask, const dev_aov_planes& out,
                        unsigned long long* counters, hipStream_t stream);
 
+// the ID-matte pass (mattes.hip k_matte): the planes of yrt_render_mattes, per key (in the
+// order of YRT_MATTE_*) and layer an int4 plane of ids and a float4 plane of coverages, ranks
+// 4l..4l+3, window layout and out_stride of launch_render; only the planes of the keys in
+// `key_mask` and of the first `layers` (1 or 2) layers are read or written. `dropped` is the
+// pass's own device buffer of matte_drop_slots lines of matte_drop_stride u64, the first
+// matte_key_count of a line the keys' dropped samples; the caller zeroes it and the counter
+// lines before the launch, and adds the lines up afterwards. An empty window launches nothing.
+enum matte_key { matte_instance = 0, matte_material = 1, matte_shape = 2, matte_key_count = 3 };
+constexpr int matte_layers_max = 2;
+constexpr int matte_drop_slots = 256;
+constexpr int matte_drop_stride = 4;
+struct dev_matte_planes {
+    void* ids[matte_key_count][matte_layers_max];
+    void* coverage[matte_key_count][matte_layers_max];
+};
+hipError_t launch_mattes(const device_scene& ds, const dev_render_args& args, unsigned key_mask, int layers,
+                         const dev_matte_planes& out, unsigned long long* dropped, unsigned long long* counters,
+                         hipStream_t stream);
+
 // mirror levels the megakernel records per lane (render.hip); the wavefront pipeline
 // keeps per-level records in HBM and takes any max_depth
 constexpr int megakernel_max_depth = 16;
