@@ -1349,7 +1349,6 @@ __device__ __forceinline__ bool packet_first_list(const dev_scene_view& S, const
     hr.dist = tmax;
     return true;
 }
-#undef YRT_OCT_DISPATCH
 
 // A wide record through the scalar cache: its first 112 bytes (bounds and child words:
 // x16 + x8 + x4, 28 SGPRs instead of 32) -- the slot count in the last row is implied by
@@ -1773,5 +1772,229 @@ __device__ __forceinline__ bool packet_occluded_wide2(const dev_scene_view& S, c
 #endif
     return (done & me) != 0;
 }
+
+// ---- the same any hit as nested loops (YRT_ANY_NESTED, default 1) ----
+// packet_occluded_wide2 is one loop steered by state (level, kind, sp == base, inst_keep,
+// finished) with a second loop inside it for "the next item"; here the levels are loops inside
+// one another, as in packet_first_list:
+//
+//   instance-level walk, floor 0: descent on tbase (the tree, or a bundle's list records)
+//       at an instance-level leaf: for each kept instance in slot order, while a lane of the
+//       leaf is still walking
+//           enter it; shape walk, floor = the sp at leaf entry: descent, leaf, pop
+//       the world ray back, once per leaf
+//       pop at the instance level
+//
+// Every lane sees the same box and primitive tests on the same values as in
+// packet_occluded_wide2 (the bodies are its bodies), so the answer per lane is the same. What
+// goes is the state the flat loop sets and tests again at every transition: the floor is a loop
+// invariant, the shape's kind and octant are invariants of the shape loop, the triangle
+// table's address is made once per triangle leaf instead of once per triangle, and an
+// instance-level leaf whose lanes are all answered is left instead of entering its remaining
+// instances for no lane.
+//
+// Registers (the fused caller sits at 64 VGPRs and the parent's 40 SGPR spills):
+// `live` and `done` are one mask, kept as `gone` = ~(live & ~done) -- the lanes not walking,
+// the form the descent and the pops take (every use in the flat walk is live & ~done or its
+// complement) -- and the lane's own `live` is made again at the end from the ray; the leaf's
+// first instance and its keep bits are one scalar; the instance-level descent (1.1 records per
+// walk at c4) is the compiled loop with the run-time octant select, one copy instead of nine
+// of the generated assembly, so no world octant is held and the code is 9 descents, not 18;
+// an instance's octant is taken from its own 1/d, identity frames included.
+// 0: shadow_item_light calls packet_occluded_wide2 as before (tools/build_variants.py "flatany").
+#if !defined(YRT_ANY_NESTED)  // (its non-default build is the `flatany` library of tools/build_variants.py)
+#define YRT_ANY_NESTED 1
+#endif
+template <int LDSN = 0, bool ASM = false>
+__device__ __forceinline__ bool packet_occluded_nested(const dev_scene_view& S, const ray3& wray, bool valid,
+                                                       const float4* lds = nullptr, const f4* tbase = nullptr,
+                                                       uint32_t troot = 0, unsigned long long pre_done = 0) {
+    const unsigned long long live = ballot(valid && !is_nan(wray.tmin) && !is_nan(wray.tmax));
+    if (!live) return false;
+    // pre_done: lanes answered already (their shadow ray is culled: reported occluded)
+    if (!(live & ~pre_done)) return lane_in(pre_done);
+    const vec3f wo = wray.o, wd = wray.d;
+    const vec3f wi = rcp3(wd, live);
+    // tmin and tmax in registers of their own: the item's tmin is a compile-time constant, and
+    // the walk built around it spills a VGPR in the fused caller's shading (packet_first_list)
+    float tmin = wray.tmin, tmax = wray.tmax;
+    asm volatile("" : "+v"(tmin), "+v"(tmax));
+    vec3f co = wo, cd = wd, ci = wi;
+    int stk_word = 0, stk_mlo = 0, stk_mhi = 0;
+    // gone: the lanes not walking -- outside `live`, culled, or occluded (~gone is
+    // packet_occluded_wide2's live & ~done)
+    unsigned long long gone = ~(live & ~pre_done);
+    int sp = 0;
+    if (!tbase) tbase = S.wnodes, troot = (uint32_t)S.wtop_root;
+    // the instance level walks a shadow bundle's list in the bundle records' leaf format
+    // (bundle_leaf_word), else the tree's: the bits of a leaf word that are its first instance --
+    // the rest of a tree leaf's index field is a bundle leaf's skip bits -- as one scalar
+    uint32_t first_bits = (S.inst_masks && tbase != S.wnodes) ? bundle_first_mask : wide_index_mask;
+    first_bits = (uint32_t)uniform((int)first_bits);
+    asm volatile("" : "+s"(first_bits));
+    // the current item: a child word (a wide node's byte offset, or a leaf)
+    uint32_t cur = troot;
+    unsigned long long mask = ~gone;
+    // the instance-local direction of every instance whose rotation is the identity, once per
+    // walk (packet_occluded_wide2)
+    vec3f icd, ici;
+    enter_direction(frame3f{{1, 0, 0}, {0, 1, 0}, {0, 0, 1}, {0, 0, 0}}, wd, live, icd, ici);
+    unsigned nsteps0 = 0, nsteps1 = 0;
+#ifdef YRT_WIDE_STATS
+    unsigned ws[16] = {1, 0, 0, 0, 0, 0, 0, 0};
+#endif
+    // ---- the instance-level walk: the world ray, floor 0 ----
+    for (;;) {
+        if (!(cur & wide_leaf)) {
+            DBG_CHECK((tbase != S.wnodes || cur < (uint32_t)S.nwnodes * wide_record_bytes) && sp >= 0 && sp < 61, 4,
+                      (int)cur, sp, 0, 0, 0);
+            // (the compiled loop, the octant selected per lane at run time: bit for bit the
+            // octant copies' products, box_oct)
+            wide_descend<8, LDSN, false>(tbase, lds, co, ci, tmin, tmax, cur, mask, sp, stk_word, stk_mlo, stk_mhi, 0,
+                                         gone, nsteps0);
+        }
+        if (mask) {
+            // ---- an instance-level leaf: its kept instances in slot order ----
+            // the first instance above the 7 keep bits, one scalar: a shadow bundle's leaf leaves
+            // out the instances its hull excludes (its skip bits, wavefront.hip k_bundle_lists);
+            // a tree leaf: none
+            uint32_t insts = (cur & first_bits) << 7 | (((1u << ((cur >> wide_count_shift) & 7u)) - 1u) &
+                                                        ~((cur & wide_index_mask & ~first_bits) >> bundle_skip_shift));
+            insts = (uint32_t)uniform((int)insts);
+            asm volatile("" : "+s"(insts));
+            const unsigned long long leaf_lanes = mask;
+            const int base = sp;  // the shape walks' floor
+            // (the leaf's instances, checked once for the leaf: with the check per entered instance
+            // the diagnostic build's compiled descents get vector registers for scalar operands)
+            DBG_CHECK((int)(insts >> 7) + (int)((cur >> wide_count_shift) & 7u) <= S.ninst, 6, (int)(insts >> 7),
+                      (int)((cur >> wide_count_shift) & 7u), sp, base, 0);
+            // (no lane of the leaf left: the remaining instances would be entered for nothing)
+            while ((insts & 0x7fu) && (leaf_lanes & ~gone)) {
+                const int k = (int)(insts >> 7) + __builtin_ctz(insts & 0x7fu);
+                insts &= insts - 1u;  // (the lowest set bit is a keep bit)
+                float4 fr[winst_rows];
+                ld_records_at<winst_rows>(S.winst, (unsigned)(winst_rows * k), fr);
+                const frame3f f = {xyz(fr[0]), xyz(fr[1]), xyz(fr[2]), xyz(fr[3])};
+                co = transform_point_inverse(f, wo);
+                const bool ident = (uniform(ibits(fr[0].w)) & (int)inst_identity_bit) != 0;
+                if (ident)
+                    cd = icd, ci = ici;
+                else
+                    enter_direction(f, wd, ~gone, cd, ci);
+                const uint32_t rk = (uint32_t)uniform(ibits(fr[1].w));
+                cur = rk & 0x3fffffffu;  // the shape's wide root (a record byte offset)
+                const int kind = (int)(rk >> 30);
+                mask = leaf_lanes & ~gone;
+                {
+                    // the shape root's own box, which the wide root (its children's children)
+                    // skips (packet_occluded_wide2)
+                    float tn;
+                    mask &= ballot(box_hit6(co, ci, tmin, tmax, fr[2].w, fr[3].w, fr[4].x, fr[4].y, fr[4].z, fr[4].w,
+                                            tn));
+                }
+                WSTAT(3, 1u);
+                WSTAT(12, mask ? 0u : 1u);  // entries whose root box no lane passes
+                if (!mask) continue;
+                // the instance's octant from its own 1/d. (The identity arm's value goes through a
+                // shift pair that changes nothing: written as the one expression, the fused kernel
+                // comes out with 41 SGPR spills for its ceiling of 40 -- the allocator's choice, not
+                // a live value more.)
+                const int soct = ident ? (wave_octant(ci, ~gone) << 4) >> 4 : wave_octant(ci, ~gone);
+                // ---- the shape walk: the instance's ray, floor = base ----
+                for (;;) {
+                    if (!(cur & wide_leaf)) {
+                        DBG_CHECK(cur < (uint32_t)S.nwnodes * wide_record_bytes && sp >= 0 && sp < 61, 4, (int)cur, sp, 1,
+                                  base, 0);
+#define YRT_WD(o)                                                                                                \
+    wide_descend<o, LDSN, ASM>(S.wnodes, lds, co, ci, tmin, tmax, cur, mask, sp, stk_word, stk_mlo, stk_mhi, base, \
+                               gone, nsteps1)
+                        YRT_OCT_DISPATCH(soct, YRT_WD)
+#undef YRT_WD
+                    }
+                    if (mask) {
+                        // ---- a shape leaf: its primitives ----
+                        const int first = (int)(cur & wide_index_mask);
+                        const int count = (int)((cur >> wide_count_shift) & 7u);
+                        DBG_CHECK(first >= 0 && first + count <= S.nsprims, 5, first, count, 1, kind, sp);
+                        const bool inl = lane_in(mask);
+                        int leaf_hit = 0;
+                        WSTAT(4, 1u);
+                        WSTAT(5, (unsigned)count);
+                        if (kind == kind_triangles) {
+                            // the table's address, once per leaf (held across the descent it
+                            // costs the kernel two more SGPR spills)
+                            const f4* abase = sgpr_ptr(reinterpret_cast<const f4*>(S.aprims));
+                            asm volatile("" : "+s"(abase));
+                            for (int i = first; i < first + count; i++) {
+                                float t, w1, w2;
+                                // v0, e1, e2 as 9 packed dwords (yrt_device.h aprims): 9 SGPRs, not 12
+                                sgpr8 a;
+                                int b;
+                                asm volatile("s_load_dwordx8 %0, %2, %3\n s_load_dword %1, %2, %3 offset:0x20\n"
+                                             " s_waitcnt lgkmcnt(0)"
+                                             : "=&s"(a), "=&s"(b)
+                                             : "s"(abase), "s"(uniform(i * 36)));
+                                const vec3f tv0 = {__int_as_float(a[0]), __int_as_float(a[1]), __int_as_float(a[2])};
+                                const vec3f te1 = {__int_as_float(a[3]), __int_as_float(a[4]), __int_as_float(a[5])};
+                                const vec3f te2 = {__int_as_float(a[6]), __int_as_float(a[7]), __int_as_float(b)};
+                                // (per lane, not tri_hit_mask: packet_occluded_wide2)
+                                const bool h = tri_hit_nb<true>(co, cd, tmin, tmax, tv0, te1, te2, t, w1, w2, inl, mask);
+                                leaf_hit |= (h && inl) ? 1 : 0;
+                            }
+                        } else {
+                            for (int i = first; i < first + count; i++) {
+                                float4 pv[3];
+                                ld_records_at<3>(S.sprims, (unsigned)(3 * i), pv);
+                                float t;
+                                vec4f ew;
+                                const ray3 lr = {co, cd, tmin, tmax};
+                                const bool h = kind == kind_lines
+                                                   ? line_hit(lr, xyz(pv[0]), xyz(pv[1]), pv[1].w, pv[2].x, t, ew)
+                                                   : point_hit(lr, xyz(pv[0]), pv[1].x, t, ew);
+                                leaf_hit |= (h && inl) ? 1 : 0;
+                            }
+                        }
+                        gone |= ballot(leaf_hit != 0);
+                        if (gone == ~0ull) goto walked;  // every lane is answered: the walk ends here
+                    }
+                    // ---- pop inside the shape, down to the leaf's floor ----
+                    [[maybe_unused]] const int sp0 = sp;
+                    int n = 0;
+                    const bool more = inner_pop(base, gone, n, mask, sp, stk_word, stk_mlo, stk_mhi);
+                    WSTAT(6, (unsigned)(sp0 - sp));
+                    WSTAT(7, (unsigned)(sp0 - sp) - (more ? 1u : 0u));
+                    if (!more) break;
+                    cur = (uint32_t)n;
+                }
+            }
+            // the world ray back, once per leaf
+            co = wo;
+            cd = wd;
+            ci = wi;
+        }
+        // ---- pop at the instance level ----
+        [[maybe_unused]] const int sp0 = sp;
+        int n = 0;
+        const bool more = inner_pop(0, gone, n, mask, sp, stk_word, stk_mlo, stk_mhi);
+        WSTAT(6, (unsigned)(sp0 - sp));
+        WSTAT(7, (unsigned)(sp0 - sp) - (more ? 1u : 0u));
+        if (!more) break;
+        cur = (uint32_t)n;
+    }
+walked:
+#ifdef YRT_WIDE_STATS
+    ws[1] = nsteps0, ws[2] = nsteps1;
+    ws[8] = (unsigned)__popcll(live), ws[9] = (unsigned)__popcll(live & gone);
+    ws[10] = ~gone ? 0u : 1u, ws[11] = ~gone ? 0u : nsteps0 + nsteps1;
+    if (__lane_id() == 0) {
+        unsigned long long* line = g_wide_stats + 16 * ((blockIdx.x * 7u + threadIdx.x / 64u) & 1023u);
+        for (int i = 0; i < 13; i++) atomicAdd(line + i, (unsigned long long)ws[i]);
+    }
+#endif
+    // live & gone, with the lane's `live` made again from its own values instead of held as a
+    // mask across the walk
+    return valid && !is_nan(tmin) && !is_nan(tmax) && lane_in(gone);
+}
+#undef YRT_OCT_DISPATCH
 
 }  // namespace yrt

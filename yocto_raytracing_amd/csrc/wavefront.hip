@@ -1879,6 +1879,18 @@ __global__ __launch_bounds__(256) void k_list_stats(wf_buffers B, int ntiles, in
 #define YRT_SHADOW_LDS_RECORDS 85
 #endif
 
+// the any hit of the persistent any-hit grids' items: the walk as nested loops
+// (packet_occluded_nested) where the records come through the scalar cache; the LDS-staged
+// opt-in (LDSN > 0) and YRT_ANY_NESTED=0 keep the flat loop (packet_occluded_wide2)
+template <int LDSN>
+__device__ __forceinline__ bool item_any_hit(const dev_scene_view& S, const ray3& sr, bool valid, const float4* lds_nodes,
+                                             const f4* tbase, uint32_t troot, unsigned long long culled) {
+    if constexpr (YRT_ANY_NESTED != 0 && LDSN == 0)
+        return packet_occluded_nested<0, true>(S, sr, valid, lds_nodes, tbase, troot, culled);
+    else
+        return packet_occluded_wide2<LDSN, true>(S, sr, valid, lds_nodes, tbase, troot, culled);
+}
+
 // one light of a 64-sample item of the persistent any-hit grids (k_shadow_persist and
 // k_shadow_shade_persist): the shadow ray of lane's sample idx = bx * 64 + lane towards light
 // li, and whether it is occluded (a culled ray counts as occluded). valid: the lane has a ray.
@@ -1943,7 +1955,7 @@ __device__ __forceinline__ bool shadow_item_light(const dev_scene_view& S, const
     // as occluded, k_shade skips the light
     return all_culled ? true
                      : lc == 0 ? ((culled >> lane) & 1ull) != 0
-                               : packet_occluded_wide2<LDSN, true>(S, sr, valid, lds_nodes, tbase, troot, culled);
+                               : item_any_hit<LDSN>(S, sr, valid, lds_nodes, tbase, troot, culled);
 }
 
 template <int LDSN>
