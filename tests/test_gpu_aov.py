@@ -327,10 +327,16 @@ def test_row_padding_is_not_written(yrt):
     nan_bits = dev["ids"][0, 0, 0].cpu().numpy().view(np.uint32)
     dev_scene(yrt, "simple").render_aovs_into(p, {n: a.data_ptr() for n, a in dev.items()}, device_memory=True)
     torch.cuda.synchronize()
+    host = {n: np.zeros((th, stride, 4), np.float32) for n in ALL_AOVS}
+    for a in host.values():
+        a.view(np.uint32)[...] = 0x7fc01234  # the caller's bytes of a host plane's padding
+    dev_scene(yrt, "simple").render_aovs_into(p, {n: a.ctypes.data for n, a in host.items()}, device_memory=False)
     for n in ALL_AOVS:
         a = dev[n].cpu().numpy()
         assert (a[:, tw:].view(np.uint32) == nan_bits).all(), n
         np.testing.assert_array_equal(a[:, :tw].view(np.uint32), full[n][y0:y0 + th, x0:x0 + tw].view(np.uint32))
+        assert (host[n][:, tw:].view(np.uint32) == 0x7fc01234).all(), n
+        np.testing.assert_array_equal(host[n][:, :tw].view(np.uint32), full[n][y0:y0 + th, x0:x0 + tw].view(np.uint32))
 
 
 def test_normal_alone_with_every_other_plane_null(yrt):

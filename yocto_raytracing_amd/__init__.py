@@ -240,20 +240,18 @@ class DeviceScene:
     def render_into(self, params: RenderParams, out_ptr: int, device_memory: bool = True,
                     stream: Optional[int] = None) -> None:
         """Launch raytrace() into a caller buffer (device pointer by default), stream ordered."""
-        mem = N.YRT_MEM_DEVICE if device_memory else N.YRT_MEM_HOST
-        check(N.lib.yrt_render(self._h, C.byref(params), C.c_void_p(out_ptr), mem,
+        check(N.lib.yrt_render(self._h, C.byref(params), C.c_void_p(out_ptr), _mem(device_memory),
                                C.c_void_p(stream or 0)), "yrt_render")
 
     def render_aovs_into(self, params: RenderParams, planes: dict, device_memory: bool = True,
                          stream: Optional[int] = None) -> None:
         """Launch the AOV pass (yrt_render_aovs) into caller planes {name: pointer}, 16 bytes
         per pixel each in render_into's layout; only the named AOVs are computed."""
-        mask, ap = _aov_mask(planes), N.AovPlanes()
+        mask, ap = _name_mask(planes, N.AOVS, "AOV"), N.AovPlanes()
         for name, ptr in planes.items():
             ap.plane[N.AOVS[name]] = ptr
-        mem = N.YRT_MEM_DEVICE if device_memory else N.YRT_MEM_HOST
-        check(N.lib.yrt_render_aovs(self._h, C.byref(params), mask, C.byref(ap), mem, C.c_void_p(stream or 0)),
-              "yrt_render_aovs")
+        check(N.lib.yrt_render_aovs(self._h, C.byref(params), mask, C.byref(ap), _mem(device_memory),
+                                    C.c_void_p(stream or 0)), "yrt_render_aovs")
 
     def render_mattes_into(self, params: RenderParams, planes: dict, layers: int, device_memory: bool = True,
                            stream: Optional[int] = None) -> None:
@@ -261,7 +259,7 @@ class DeviceScene:
         per layer], "coverage": [pointer per layer]}}, 16 bytes per pixel each in render_into's
         layout (int32 x 4 and float32 x 4: ranks 4 * layer .. 4 * layer + 3); only the named keys
         are computed, all from one walk."""
-        mask, mp = _matte_mask(planes), N.MattePlanes()
+        mask, mp = _name_mask(planes, N.MATTE_KEYS, "matte key"), N.MattePlanes()
         for key, kp in planes.items():
             for what, dst in (("ids", mp.ids), ("coverage", mp.coverage)):
                 ptrs = list(kp[what])
@@ -269,8 +267,7 @@ class DeviceScene:
                     raise ValueError(f"at most {N.YRT_MATTE_LAYERS_MAX} layers per matte key")
                 for l, ptr in enumerate(ptrs):
                     dst[N.MATTE_KEYS[key]][l] = ptr
-        mem = N.YRT_MEM_DEVICE if device_memory else N.YRT_MEM_HOST
-        check(N.lib.yrt_render_mattes(self._h, C.byref(params), mask, int(layers), C.byref(mp), mem,
+        check(N.lib.yrt_render_mattes(self._h, C.byref(params), mask, int(layers), C.byref(mp), _mem(device_memory),
                                       C.c_void_p(stream or 0)), "yrt_render_mattes")
 
     def matte_dropped(self) -> dict:
@@ -285,12 +282,11 @@ class DeviceScene:
         """Launch raytrace() with its shading passes (yrt_render_passes) into caller planes
         {name: pointer}, RGBA float32 each in render_into's layout; only the named passes are
         written. `beauty_ptr`, when given, receives render_into's image from the same walk."""
-        mask, pp = _pass_mask(planes), N.PassPlanes()
+        mask, pp = _name_mask(planes, N.PASSES, "pass"), N.PassPlanes()
         for name, ptr in planes.items():
             pp.plane[N.PASSES[name]] = ptr
-        mem = N.YRT_MEM_DEVICE if device_memory else N.YRT_MEM_HOST
-        check(N.lib.yrt_render_passes(self._h, C.byref(params), mask, C.byref(pp), C.c_void_p(beauty_ptr or 0), mem,
-                                      C.c_void_p(stream or 0)), "yrt_render_passes")
+        check(N.lib.yrt_render_passes(self._h, C.byref(params), mask, C.byref(pp), C.c_void_p(beauty_ptr or 0),
+                                      _mem(device_memory), C.c_void_p(stream or 0)), "yrt_render_passes")
 
     def render_light_groups_into(self, params: RenderParams, groups: Sequence[int], group_ptrs: Sequence[int],
                                  ambient_ptr: Optional[int] = None, beauty_ptr: Optional[int] = None,
@@ -305,18 +301,16 @@ class DeviceScene:
             lp.group[g] = ptr
         lp.ambient, lp.beauty = ambient_ptr or None, beauty_ptr or None
         gof = (C.c_int * max(len(groups), 1))(*[int(g) for g in groups])
-        mem = N.YRT_MEM_DEVICE if device_memory else N.YRT_MEM_HOST
-        check(N.lib.yrt_render_light_groups(self._h, C.byref(params), gof, len(groups), ngroups, C.byref(lp), mem,
-                                            C.c_void_p(stream or 0)), "yrt_render_light_groups")
+        check(N.lib.yrt_render_light_groups(self._h, C.byref(params), gof, len(groups), ngroups, C.byref(lp),
+                                            _mem(device_memory), C.c_void_p(stream or 0)), "yrt_render_light_groups")
 
     def shade_rays_into(self, params: RenderParams, rays_ptr: int, n: int, out_ptr: int, device_memory: bool = True,
                         stream: Optional[int] = None) -> None:
         """Launch shade() for n caller rays (yrt_shade_rays): `rays_ptr` n x 8 float32 {o.xyz,
         d.xyz, tmin, tmax}, `out_ptr` n x RGBA float32, both device pointers by default, stream
         ordered. Of `params`, ambient, max_depth, algorithm and timing are used."""
-        mem = N.YRT_MEM_DEVICE if device_memory else N.YRT_MEM_HOST
-        check(N.lib.yrt_shade_rays(self._h, C.byref(params), C.c_void_p(rays_ptr), int(n), C.c_void_p(out_ptr), mem,
-                                   C.c_void_p(stream or 0)), "yrt_shade_rays")
+        check(N.lib.yrt_shade_rays(self._h, C.byref(params), C.c_void_p(rays_ptr), int(n), C.c_void_p(out_ptr),
+                                   _mem(device_memory), C.c_void_p(stream or 0)), "yrt_shade_rays")
 
     def last_timings(self) -> dict:
         """per-phase GPU ms of the last render with timing=True: {phase: (ms, launches)}"""
@@ -359,8 +353,8 @@ class MultiScene:
 
     def render_into(self, params: RenderParams, out_ptr: int, device_memory: bool = False) -> None:
         """raytrace() of the whole frame into a host buffer, or a device buffer on devices[0]"""
-        mem = N.YRT_MEM_DEVICE if device_memory else N.YRT_MEM_HOST
-        check(N.lib.yrt_multi_render(self._h, C.byref(params), C.c_void_p(out_ptr), mem), "yrt_multi_render")
+        check(N.lib.yrt_multi_render(self._h, C.byref(params), C.c_void_p(out_ptr), _mem(device_memory)),
+              "yrt_multi_render")
 
     def last_stats(self) -> dict:
         s = Stats()
@@ -427,6 +421,31 @@ def _device_scene(scn, device: int = 0) -> DeviceScene:
     return scn.upload(device)
 
 
+def _mem(device_memory: bool) -> int:
+    return N.YRT_MEM_DEVICE if device_memory else N.YRT_MEM_HOST
+
+
+def _name_mask(names, table: dict, noun: str) -> int:
+    """the bit mask of `names` in `table` (N.AOVS, N.MATTE_KEYS or N.PASSES: name -> bit); an
+    unknown name, or no name at all, raises before any native call"""
+    names = list(names)
+    bad = [n for n in names if n not in table]
+    if bad or not names:
+        raise ValueError((f"unknown {noun} {bad[0]!r}" if bad else f"no {noun} named") + f" (one of {', '.join(table)})")
+    mask = 0
+    for n in names:
+        mask |= 1 << table[n]
+    return mask
+
+
+def _window_shape(ds: DeviceScene, p: RenderParams, window) -> tuple:
+    """(h, w) of the arrays a render of `p` fills: the window's, or the whole image's"""
+    W, H = ds.image_size(p)
+    if window is None:
+        return H, W
+    return window[3] or H - window[1], window[2] or W - window[0]
+
+
 def raytrace(scn, amb: Sequence[float] = (0.1, 0.1, 0.1), resolution: int = 720, samples: int = 1,
              *, width: int = 0, max_depth: int = 16, camera: int = 0, window=None,
              count_work: bool = False, return_stats: bool = False, algorithm: str = "wavefront",
@@ -454,28 +473,12 @@ def raytrace(scn, amb: Sequence[float] = (0.1, 0.1, 0.1), resolution: int = 720,
     ds = _device_scene(scn)
     p = render_params(amb, resolution, samples, width=width, max_depth=max_depth, camera=camera,
                       window=window, count_work=count_work, algorithm=algorithm)
-    W, H = ds.image_size(p)
-    if window is None:
-        w, h = W, H
-    else:
-        w, h = window[2] or W - window[0], window[3] or H - window[1]
+    h, w = _window_shape(ds, p, window)
     img = np.zeros((h, w, 4), np.float32)
     ds.render_into(p, img.ctypes.data, device_memory=False)
     if return_stats:
         return img, ds.last_stats()
     return img
-
-
-def _aov_mask(names) -> int:
-    """the YRT_AOV_* bit mask of AOV names; an unknown name raises before any native call"""
-    names = list(names)
-    bad = [n for n in names if n not in N.AOVS]
-    if bad or not names:
-        raise ValueError((f"unknown AOV {bad[0]!r}" if bad else "no AOV named") + f" (one of {', '.join(N.AOVS)})")
-    mask = 0
-    for n in names:
-        mask |= 1 << N.AOVS[n]
-    return mask
 
 
 def render_aovs(scn, resolution: int = 720, samples: int = 1, *, aovs: Sequence[str] = tuple(N.AOVS),
@@ -484,30 +487,13 @@ def render_aovs(scn, resolution: int = 720, samples: int = 1, *, aovs: Sequence[
     {value.xyz premultiplied by coverage, coverage} for "depth", "position", "normal",
     "texcoord" and "albedo", int32 {instance, element, material, shape} of the pixel's first
     sample for "ids" (-1 on a miss). `scn` is a Scene or a DeviceScene, as for raytrace."""
-    _aov_mask(aovs)
+    _name_mask(aovs, N.AOVS, "AOV")
     ds = _device_scene(scn, device)
     p = render_params(resolution=resolution, samples=samples, width=width, camera=camera, window=window)
-    W, H = ds.image_size(p)
-    if window is None:
-        w, h = W, H
-    else:
-        w, h = window[2] or W - window[0], window[3] or H - window[1]
+    h, w = _window_shape(ds, p, window)
     out = {n: np.zeros((h, w, 4), np.int32 if n == "ids" else np.float32) for n in aovs}
     ds.render_aovs_into(p, {n: a.ctypes.data for n, a in out.items()}, device_memory=False)
     return out
-
-
-def _matte_mask(names) -> int:
-    """the YRT_MATTE_* bit mask of key names; an unknown name raises before any native call"""
-    names = list(names)
-    bad = [n for n in names if n not in N.MATTE_KEYS]
-    if bad or not names:
-        raise ValueError((f"unknown matte key {bad[0]!r}" if bad else "no matte key named") +
-                         f" (one of {', '.join(N.MATTE_KEYS)})")
-    mask = 0
-    for n in names:
-        mask |= 1 << N.MATTE_KEYS[n]
-    return mask
 
 
 def render_mattes(scn, resolution: int = 720, samples: int = 1, *, keys: Sequence[str] = ("instance",),
@@ -520,17 +506,13 @@ def render_mattes(scn, resolution: int = 720, samples: int = 1, *, keys: Sequenc
     and counted under "dropped". matte() turns a key's arrays and a set of ids into a mask that
     is box filtered as the beauty is. `scn` is a Scene or a DeviceScene, as for raytrace."""
     keys = list(keys)
-    _matte_mask(keys)
+    _name_mask(keys, N.MATTE_KEYS, "matte key")
     if isinstance(ranks, bool) or ranks not in (4, 8):
         raise ValueError(f"ranks must be 4 or 8, not {ranks!r}")
     layers = int(ranks) // 4
     ds = _device_scene(scn, device)
     p = render_params(resolution=resolution, samples=samples, width=width, camera=camera, window=window)
-    W, H = ds.image_size(p)
-    if window is None:
-        w, h = W, H
-    else:
-        w, h = window[2] or W - window[0], window[3] or H - window[1]
+    h, w = _window_shape(ds, p, window)
     planes = {k: {"ids": [np.zeros((h, w, 4), np.int32) for _ in range(layers)],
                   "coverage": [np.zeros((h, w, 4), np.float32) for _ in range(layers)]} for k in keys}
     ds.render_mattes_into(p, {k: {n: [a.ctypes.data for a in v] for n, v in kp.items()} for k, kp in planes.items()},
@@ -555,18 +537,6 @@ def matte(m: dict, ids) -> np.ndarray:
     return acc
 
 
-def _pass_mask(names) -> int:
-    """the YRT_PASS_* bit mask of pass names; an unknown name raises before any native call"""
-    names = list(names)
-    bad = [n for n in names if n not in N.PASSES]
-    if bad or not names:
-        raise ValueError((f"unknown pass {bad[0]!r}" if bad else "no pass named") + f" (one of {', '.join(N.PASSES)})")
-    mask = 0
-    for n in names:
-        mask |= 1 << N.PASSES[n]
-    return mask
-
-
 def render_passes(scn, amb: Sequence[float] = (0.1, 0.1, 0.1), resolution: int = 720, samples: int = 1, *,
                   passes: Sequence[str] = tuple(N.PASSES), beauty: bool = True, width: int = 0, max_depth: int = 16,
                   camera: int = 0, window=None, algorithm: str = "wavefront", devices=None, device: int = 0) -> dict:
@@ -576,17 +546,13 @@ def render_passes(scn, amb: Sequence[float] = (0.1, 0.1, 0.1), resolution: int =
     with `beauty` the image raytrace gives, under "beauty", from the same render. At one sample
     per pixel beauty == (direct + reflection) + ambient in float32. One GPU: `devices` is not
     supported (shard with a window or bands instead)."""
-    _pass_mask(passes)
+    _name_mask(passes, N.PASSES, "pass")
     if devices is not None:
         raise ValueError("render_passes renders on one GPU: devices= is not supported")
     ds = _device_scene(scn, device)
     p = render_params(amb, resolution, samples, width=width, max_depth=max_depth, camera=camera, window=window,
                       algorithm=algorithm)
-    W, H = ds.image_size(p)
-    if window is None:
-        w, h = W, H
-    else:
-        w, h = window[2] or W - window[0], window[3] or H - window[1]
+    h, w = _window_shape(ds, p, window)
     out = {n: np.zeros((h, w, 4), np.float32) for n in passes}
     img = np.zeros((h, w, 4), np.float32) if beauty else None
     ds.render_passes_into(p, {n: a.ctypes.data for n, a in out.items()},
@@ -631,11 +597,7 @@ def render_light_groups(scn, amb: Sequence[float] = (0.1, 0.1, 0.1), resolution:
     ds = _device_scene(scn, device)
     p = render_params(amb, resolution, samples, width=width, max_depth=max_depth, camera=camera, window=window,
                       algorithm=algorithm)
-    W, H = ds.image_size(p)
-    if window is None:
-        w, h = W, H
-    else:
-        w, h = window[2] or W - window[0], window[3] or H - window[1]
+    h, w = _window_shape(ds, p, window)
     out = {"groups": [np.zeros((h, w, 4), np.float32) for _ in range(ngroups)]}
     if ambient:
         out["ambient"] = np.zeros((h, w, 4), np.float32)

@@ -14,6 +14,7 @@
 
 #include "../../include/yrt.h"
 #include "matte_args.h"
+#include "plane_staging.h"
 #include "yrt_render.h"
 
 struct yrt_host_scene {
@@ -116,6 +117,72 @@ resolved_window resolve(const yrt::device_scene& ds, const yrt_render_params& p)
     r.th = p.tile_h > 0 ? p.tile_h : my_bands * p.band;
     if (r.x0 + r.tw > r.W) throw std::invalid_argument("window wider than image");
     return r;
+}
+
+// the kernels' frame arguments of p and its resolved window; refuses an out_stride below the
+// window's width. With `shading` the ambient and the recursion depth too: the AOV and matte
+// passes, which shade nothing, leave them zero. A ray batch (yrt_shade_rays) has no camera and
+// no window, r == nullptr, and takes the shading part alone.
+yrt::dev_render_args frame_args(const yrt_scene* s, const yrt_render_params& p, const resolved_window* r, bool shading) {
+    yrt::dev_render_args a = {};
+    if (shading) {
+        for (int k = 0; k < 3; k++) a.amb[k] = p.ambient[k];
+        a.max_depth = p.max_depth > 0 ? p.max_depth : 16;
+    }
+    if (!r) return a;
+    a.cam = yrt::make_dev_camera(s->ds->cameras[p.camera]);
+    a.width = r->W;
+    a.height = r->H;
+    a.samples = p.samples;
+    a.x0 = r->x0;
+    a.tile_w = r->tw;
+    a.y0 = r->y0;
+    a.tile_h = r->th;
+    a.band = p.band;
+    a.band_stride = p.band_stride;
+    a.band_offset = p.band_offset;
+    a.out_stride = p.out_stride > 0 ? p.out_stride : r->tw;
+    if (a.out_stride < r->tw) throw std::invalid_argument("out_stride smaller than the window width");
+    return a;
+}
+
+void zero_counters(yrt_scene* s, hipStream_t st) {
+    hip_check(hipMemsetAsync(s->counters, 0, yrt::cnt_slots * yrt::cnt_count * sizeof(unsigned long long), st),
+              "hipMemsetAsync");
+}
+
+// timing 1: start a new record; 2: keep accumulating across calls (bench loops)
+void start_timer(yrt_scene* s, const yrt_render_params& p) {
+    if (!(p.timing == 2 && s->ds->timer.on)) s->ds->timer.reset(p.timing != 0);
+}
+
+// Host planes: device staging of their own (the handle's scratch stays yrt_render's) -- one
+// block for the planes of `list`, uploaded first where the rows are padded (padding columns
+// keep the caller's bytes), handed to `launch`, copied back when it succeeded, and released.
+// The block is released only after the stream has drained, on every way out; the launch's
+// error is reported before the drain's.
+template <class Launch>
+void stage_host_planes(const yrt::plane_list& list, bool padded, hipStream_t st, const char* alloc_what,
+                       const char* render_what, Launch&& launch) {
+    void* stage = nullptr;
+    hip_check(hipMalloc(&stage, list.bytes), alloc_what);
+    hipError_t e = hipSuccess;
+    try {
+        for (int k = 0; k < list.count && padded; k++)
+            hip_check(hipMemcpyAsync(list.plane(k, stage), list.items[k].host, list.plane_bytes, hipMemcpyHostToDevice, st),
+                      "hipMemcpyAsync");
+        e = launch(stage);
+        for (int k = 0; k < list.count && e == hipSuccess; k++)
+            e = hipMemcpyAsync(list.items[k].host, list.plane(k, stage), list.plane_bytes, hipMemcpyDeviceToHost, st);
+    } catch (...) {
+        (void)hipStreamSynchronize(st);
+        (void)hipFree(stage);
+        throw;
+    }
+    const hipError_t e2 = hipStreamSynchronize(st);
+    (void)hipFree(stage);
+    hip_check(e, render_what);
+    hip_check(e2, "hipStreamSynchronize");
 }
 
 }  // namespace
@@ -514,30 +581,12 @@ int yrt_render(yrt_scene* s, const yrt_render_params* p, float* out, int mem, vo
         auto r = resolve(*s->ds, *p);
         hipStream_t st = (hipStream_t)stream;
         hip_check(hipSetDevice(s->ds->device), "hipSetDevice");
-        yrt::dev_render_args a = {};
-        a.cam = yrt::make_dev_camera(s->ds->cameras[p->camera]);
-        for (int k = 0; k < 3; k++) a.amb[k] = p->ambient[k];
-        a.width = r.W;
-        a.height = r.H;
-        a.samples = p->samples;
-        a.max_depth = p->max_depth > 0 ? p->max_depth : 16;
-        a.x0 = r.x0;
-        a.tile_w = r.tw;
-        a.y0 = r.y0;
-        a.tile_h = r.th;
-        a.band = p->band;
-        a.band_stride = p->band_stride;
-        a.band_offset = p->band_offset;
-        a.out_stride = p->out_stride > 0 ? p->out_stride : r.tw;
-        if (a.out_stride < r.tw) throw std::invalid_argument("out_stride smaller than the window width");
+        const yrt::dev_render_args a = frame_args(s, *p, &r, true);
         size_t bytes = (size_t)a.out_stride * r.th * 4 * sizeof(float);
         void* dst = mem == YRT_MEM_DEVICE ? (void*)out : scratch(s, bytes);
         // (the wavefront algorithms zero the counter lines in their first kernel, k_chunk_setup)
-        if (p->algorithm == YRT_ALGO_MEGAKERNEL)
-            hip_check(hipMemsetAsync(s->counters, 0, yrt::cnt_slots * yrt::cnt_count * sizeof(unsigned long long), st),
-                      "hipMemsetAsync");
-        // timing 1: start a new record; 2: keep accumulating across calls (bench loops)
-        if (!(p->timing == 2 && s->ds->timer.on)) s->ds->timer.reset(p->timing != 0);
+        if (p->algorithm == YRT_ALGO_MEGAKERNEL) zero_counters(s, st);
+        start_timer(s, *p);
         if (p->algorithm == YRT_ALGO_MEGAKERNEL && s->ds->reflective && a.max_depth > yrt::megakernel_max_depth)
             throw yrt::unsupported_error("the megakernel keeps " + std::to_string(yrt::megakernel_max_depth) +
                                          " mirror levels per lane; deeper recursions need the wavefront algorithm");
@@ -574,57 +623,22 @@ int yrt_render_aovs(yrt_scene* s, const yrt_render_params* p, unsigned mask, con
         auto r = resolve(*s->ds, *p);
         hipStream_t st = (hipStream_t)stream;
         hip_check(hipSetDevice(s->ds->device), "hipSetDevice");
-        yrt::dev_render_args a = {};
-        a.cam = yrt::make_dev_camera(s->ds->cameras[p->camera]);
-        a.width = r.W;
-        a.height = r.H;
-        a.samples = p->samples;
-        a.x0 = r.x0;
-        a.tile_w = r.tw;
-        a.y0 = r.y0;
-        a.tile_h = r.th;
-        a.band = p->band;
-        a.band_stride = p->band_stride;
-        a.band_offset = p->band_offset;
-        a.out_stride = p->out_stride > 0 ? p->out_stride : r.tw;
-        if (a.out_stride < r.tw) throw std::invalid_argument("out_stride smaller than the window width");
+        const yrt::dev_render_args a = frame_args(s, *p, &r, false);
         // the counters are zeroed whatever the window: an empty one (a band offset without
         // bands) launches nothing, and yrt_last_stats must not then report the call before
-        hip_check(hipMemsetAsync(s->counters, 0, yrt::cnt_slots * yrt::cnt_count * sizeof(unsigned long long), st),
-                  "hipMemsetAsync");
+        zero_counters(s, st);
         s->last_stream = st;
         if (r.tw <= 0 || r.th <= 0) return YRT_OK;
-        yrt::dev_aov_planes dp = {};
-        if (mem == YRT_MEM_DEVICE) {
-            for (int k = 0; k < YRT_AOV_COUNT; k++) dp.plane[k] = (mask >> k & 1) ? out->plane[k] : nullptr;
-            hip_check(yrt::launch_aovs(*s->ds, a, mask, dp, s->counters, st), "aov kernel launch");
-            return YRT_OK;
-        }
-        // host planes: device staging of their own (the handle's scratch stays yrt_render's),
-        // copied back and released
-        const size_t bytes = (size_t)a.out_stride * r.th * 16;
-        struct staging {
-            void* p = nullptr;
-            ~staging() {
-                if (p) (void)hipFree(p);
-            }
-        } stage;
-        hip_check(hipMalloc(&stage.p, bytes * __builtin_popcount(mask)), "hipMalloc(aov staging)");
-        size_t used = 0;
-        for (int k = 0; k < YRT_AOV_COUNT; k++)
-            if (mask >> k & 1) dp.plane[k] = (char*)stage.p + bytes * used++;
-        // padding columns (out_stride > tile_w) keep the caller's bytes: they are staged too
-        if (a.out_stride > r.tw)
-            for (int k = 0; k < YRT_AOV_COUNT; k++)
-                if (mask >> k & 1)
-                    hip_check(hipMemcpyAsync(dp.plane[k], out->plane[k], bytes, hipMemcpyHostToDevice, st), "hipMemcpyAsync");
-        hipError_t e = yrt::launch_aovs(*s->ds, a, mask, dp, s->counters, st);
-        for (int k = 0; k < YRT_AOV_COUNT && e == hipSuccess; k++)
-            if (mask >> k & 1) e = hipMemcpyAsync(out->plane[k], dp.plane[k], bytes, hipMemcpyDeviceToHost, st);
-        // the staging is released only after the stream has drained, also on an error
-        const hipError_t e2 = hipStreamSynchronize(st);
-        hip_check(e, "aov render");
-        hip_check(e2, "hipStreamSynchronize");
+        const yrt::plane_list list = yrt::aov_plane_list(mask, *out, (size_t)a.out_stride * r.th * 16);
+        auto launch = [&](void* staging) {
+            yrt::dev_aov_planes dp = {};
+            for (int k = 0; k < list.count; k++) dp.plane[list.items[k].slot] = list.plane(k, staging);
+            return yrt::launch_aovs(*s->ds, a, mask, dp, s->counters, st);
+        };
+        if (mem == YRT_MEM_DEVICE)
+            hip_check(launch(nullptr), "aov kernel launch");
+        else
+            stage_host_planes(list, a.out_stride > r.tw, st, "hipMalloc(aov staging)", "aov render", launch);
         return YRT_OK;
     });
 }
@@ -640,69 +654,30 @@ int yrt_render_mattes(yrt_scene* s, const yrt_render_params* p, unsigned key_mas
     return guarded([&] {
         if (const char* bad = yrt::matte_args_error(key_mask, layers, out, mem)) throw std::invalid_argument(bad);
         auto r = resolve(*s->ds, *p);
-        if ((p->out_stride > 0 ? p->out_stride : r.tw) < r.tw)
-            throw std::invalid_argument("out_stride smaller than the window width");
+        const yrt::dev_render_args a = frame_args(s, *p, &r, false);  // (its refusal comes before any device call)
         hipStream_t st = (hipStream_t)stream;
         hip_check(hipSetDevice(s->ds->device), "hipSetDevice");
-        yrt::dev_render_args a = {};
-        a.cam = yrt::make_dev_camera(s->ds->cameras[p->camera]);
-        a.width = r.W;
-        a.height = r.H;
-        a.samples = p->samples;
-        a.x0 = r.x0;
-        a.tile_w = r.tw;
-        a.y0 = r.y0;
-        a.tile_h = r.th;
-        a.band = p->band;
-        a.band_stride = p->band_stride;
-        a.band_offset = p->band_offset;
-        a.out_stride = p->out_stride > 0 ? p->out_stride : r.tw;
         const size_t drop_bytes = (size_t)yrt::matte_drop_slots * yrt::matte_drop_stride * sizeof(unsigned long long);
         if (!s->matte_dropped) hip_check(hipMalloc(&s->matte_dropped, drop_bytes), "hipMalloc(matte dropped totals)");
         // the counters and the dropped totals are zeroed whatever the window: an empty one (a
         // band offset without bands) launches nothing, and must not report the call before
-        hip_check(hipMemsetAsync(s->counters, 0, yrt::cnt_slots * yrt::cnt_count * sizeof(unsigned long long), st),
-                  "hipMemsetAsync");
+        zero_counters(s, st);
         hip_check(hipMemsetAsync(s->matte_dropped, 0, drop_bytes, st), "hipMemsetAsync");
         s->last_stream = st;
         if (r.tw <= 0 || r.th <= 0) return YRT_OK;
-        yrt::dev_matte_planes dp = {};
-        if (mem == YRT_MEM_DEVICE) {
-            for (int k = 0; k < YRT_MATTE_KEY_COUNT; k++)
-                for (int l = 0; l < layers; l++)
-                    if (key_mask >> k & 1) dp.ids[k][l] = out->ids[k][l], dp.coverage[k][l] = out->coverage[k][l];
-            hip_check(yrt::launch_mattes(*s->ds, a, key_mask, layers, dp, s->matte_dropped, s->counters, st),
-                      "matte kernel launch");
-            return YRT_OK;
-        }
-        // host planes: device staging of their own (the handle's scratch stays yrt_render's),
-        // copied back and released
-        const size_t bytes = (size_t)a.out_stride * r.th * 16;
-        const yrt::matte_staging lay = yrt::matte_stage_layout(key_mask, layers, *out, bytes);
-        struct staging {
-            void* p = nullptr;
-            ~staging() {
-                if (p) (void)hipFree(p);
+        const yrt::plane_list list = yrt::matte_plane_list(key_mask, layers, *out, (size_t)a.out_stride * r.th * 16);
+        auto launch = [&](void* staging) {
+            yrt::dev_matte_planes dp = {};
+            for (int k = 0; k < list.count; k++) {
+                const int slot = list.items[k].slot;  // 4 key + 2 layer + coverage
+                (slot & 1 ? dp.coverage : dp.ids)[slot >> 2][slot >> 1 & 1] = list.plane(k, staging);
             }
-        } stage;
-        hip_check(hipMalloc(&stage.p, lay.bytes), "hipMalloc(matte staging)");
-        for (int k = 0; k < lay.count; k++) {
-            const auto& it = lay.items[k];
-            (it.coverage ? dp.coverage : dp.ids)[it.key][it.layer] = (char*)stage.p + it.offset;
-        }
-        // padding columns (out_stride > tile_w) keep the caller's bytes: they are staged too
-        if (a.out_stride > r.tw)
-            for (int k = 0; k < lay.count; k++)
-                hip_check(hipMemcpyAsync((char*)stage.p + lay.items[k].offset, lay.items[k].host, bytes,
-                                         hipMemcpyHostToDevice, st),
-                          "hipMemcpyAsync");
-        hipError_t e = yrt::launch_mattes(*s->ds, a, key_mask, layers, dp, s->matte_dropped, s->counters, st);
-        for (int k = 0; k < lay.count && e == hipSuccess; k++)
-            e = hipMemcpyAsync(lay.items[k].host, (char*)stage.p + lay.items[k].offset, bytes, hipMemcpyDeviceToHost, st);
-        // the staging is released only after the stream has drained, also on an error
-        const hipError_t e2 = hipStreamSynchronize(st);
-        hip_check(e, "matte render");
-        hip_check(e2, "hipStreamSynchronize");
+            return yrt::launch_mattes(*s->ds, a, key_mask, layers, dp, s->matte_dropped, s->counters, st);
+        };
+        if (mem == YRT_MEM_DEVICE)
+            hip_check(launch(nullptr), "matte kernel launch");
+        else
+            stage_host_planes(list, a.out_stride > r.tw, st, "hipMalloc(matte staging)", "matte render", launch);
         return YRT_OK;
     });
 }
@@ -750,67 +725,23 @@ int yrt_render_passes(yrt_scene* s, const yrt_render_params* p, unsigned mask, c
         auto r = resolve(*s->ds, *p);
         hipStream_t st = (hipStream_t)stream;
         hip_check(hipSetDevice(s->ds->device), "hipSetDevice");
-        yrt::dev_render_args a = {};
-        a.cam = yrt::make_dev_camera(s->ds->cameras[p->camera]);
-        for (int k = 0; k < 3; k++) a.amb[k] = p->ambient[k];
-        a.width = r.W;
-        a.height = r.H;
-        a.samples = p->samples;
-        a.max_depth = p->max_depth > 0 ? p->max_depth : 16;
-        a.x0 = r.x0;
-        a.tile_w = r.tw;
-        a.y0 = r.y0;
-        a.tile_h = r.th;
-        a.band = p->band;
-        a.band_stride = p->band_stride;
-        a.band_offset = p->band_offset;
-        a.out_stride = p->out_stride > 0 ? p->out_stride : r.tw;
-        if (a.out_stride < r.tw) throw std::invalid_argument("out_stride smaller than the window width");
-        if (!(p->timing == 2 && s->ds->timer.on)) s->ds->timer.reset(p->timing != 0);
-        const bool packet = p->algorithm == YRT_ALGO_WAVEFRONT;
+        const yrt::dev_render_args a = frame_args(s, *p, &r, true);
+        start_timer(s, *p);
         s->last_stream = st;
-        yrt::dev_pass_planes dp = {};
-        if (mem == YRT_MEM_DEVICE || r.tw <= 0 || r.th <= 0) {
-            // (an empty window launches nothing but the counters' memset: the planes are not touched)
-            for (int k = 0; k < YRT_PASS_COUNT; k++) dp.plane[k] = (mask >> k & 1) ? out->plane[k] : nullptr;
-            hip_check(yrt::launch_render_wavefront_passes(*s->ds, a, mask, dp, beauty, s->counters, packet, st),
-                      "passes render launch");
-            return YRT_OK;
-        }
-        // host planes: device staging of their own (the handle's scratch stays yrt_render's),
-        // copied back and released
-        const size_t bytes = (size_t)a.out_stride * r.th * 16;
-        struct staging {
-            void* p = nullptr;
-            ~staging() {
-                if (p) (void)hipFree(p);
-            }
-        } stage;
-        hip_check(hipMalloc(&stage.p, bytes * (__builtin_popcount(mask) + (beauty ? 1 : 0))), "hipMalloc(pass staging)");
-        size_t used = 0;
-        float* host[YRT_PASS_COUNT + 1] = {};
-        float* dev[YRT_PASS_COUNT + 1] = {};
-        for (int k = 0; k <= YRT_PASS_COUNT; k++) {
-            host[k] = k < YRT_PASS_COUNT ? ((mask >> k & 1) ? out->plane[k] : nullptr) : beauty;
-            if (host[k]) dev[k] = (float*)((char*)stage.p + bytes * used++);
-            if (k < YRT_PASS_COUNT) dp.plane[k] = dev[k];
-        }
-        // padding columns (out_stride > tile_w) keep the caller's bytes: they are staged too
-        if (a.out_stride > r.tw)
-            for (int k = 0; k <= YRT_PASS_COUNT; k++)
-                if (host[k]) hip_check(hipMemcpyAsync(dev[k], host[k], bytes, hipMemcpyHostToDevice, st), "hipMemcpyAsync");
-        hipError_t e = hipSuccess;
-        try {
-            e = yrt::launch_render_wavefront_passes(*s->ds, a, mask, dp, dev[YRT_PASS_COUNT], s->counters, packet, st);
-        } catch (...) {
-            (void)hipStreamSynchronize(st);  // the staging is released only after the stream has drained
-            throw;
-        }
-        for (int k = 0; k <= YRT_PASS_COUNT && e == hipSuccess; k++)
-            if (host[k]) e = hipMemcpyAsync(host[k], dev[k], bytes, hipMemcpyDeviceToHost, st);
-        const hipError_t e2 = hipStreamSynchronize(st);
-        hip_check(e, "passes render");
-        hip_check(e2, "hipStreamSynchronize");
+        const yrt::plane_list list = yrt::pass_plane_list(mask, *out, beauty, (size_t)a.out_stride * r.th * 16);
+        auto launch = [&](void* staging) {
+            yrt::dev_pass_planes dp = {};
+            float* planes[YRT_PASS_COUNT + 1] = {};  // the passes, then the beauty
+            for (int k = 0; k < list.count; k++) planes[list.items[k].slot] = (float*)list.plane(k, staging);
+            for (int k = 0; k < YRT_PASS_COUNT; k++) dp.plane[k] = planes[k];
+            return yrt::launch_render_wavefront_passes(*s->ds, a, mask, dp, planes[YRT_PASS_COUNT], s->counters,
+                                                       p->algorithm == YRT_ALGO_WAVEFRONT, st);
+        };
+        // (an empty window launches nothing but the counters' memset: the planes are not touched)
+        if (mem == YRT_MEM_DEVICE || r.tw <= 0 || r.th <= 0)
+            hip_check(launch(nullptr), "passes render launch");
+        else
+            stage_host_planes(list, a.out_stride > r.tw, st, "hipMalloc(pass staging)", "passes render", launch);
         return YRT_OK;
     });
 }
@@ -840,76 +771,25 @@ int yrt_render_light_groups(yrt_scene* s, const yrt_render_params* p, const int*
         auto r = resolve(*s->ds, *p);
         hipStream_t st = (hipStream_t)stream;
         hip_check(hipSetDevice(s->ds->device), "hipSetDevice");
-        yrt::dev_render_args a = {};
-        a.cam = yrt::make_dev_camera(s->ds->cameras[p->camera]);
-        for (int k = 0; k < 3; k++) a.amb[k] = p->ambient[k];
-        a.width = r.W;
-        a.height = r.H;
-        a.samples = p->samples;
-        a.max_depth = p->max_depth > 0 ? p->max_depth : 16;
-        a.x0 = r.x0;
-        a.tile_w = r.tw;
-        a.y0 = r.y0;
-        a.tile_h = r.th;
-        a.band = p->band;
-        a.band_stride = p->band_stride;
-        a.band_offset = p->band_offset;
-        a.out_stride = p->out_stride > 0 ? p->out_stride : r.tw;
-        if (a.out_stride < r.tw) throw std::invalid_argument("out_stride smaller than the window width");
-        if (!(p->timing == 2 && s->ds->timer.on)) s->ds->timer.reset(p->timing != 0);
-        const bool packet = p->algorithm == YRT_ALGO_WAVEFRONT;
+        const yrt::dev_render_args a = frame_args(s, *p, &r, true);
+        start_timer(s, *p);
         s->last_stream = st;
-        // the caller's planes in one list: the groups, the ambient, the beauty
-        constexpr int NP = YRT_LIGHT_GROUPS_MAX + 2;
-        float* host[NP] = {};
-        for (int g = 0; g < ngroups; g++) host[g] = out->group[g];
-        host[NP - 2] = out->ambient, host[NP - 1] = out->beauty;
-        auto planes_of = [&](float* const* v) {
+        const yrt::plane_list list = yrt::light_group_plane_list(ngroups, *out, (size_t)a.out_stride * r.th * 16);
+        auto launch = [&](void* staging) {
+            float* planes[YRT_LIGHT_GROUPS_MAX + 2] = {};  // the groups, the ambient, the beauty
+            for (int k = 0; k < list.count; k++) planes[list.items[k].slot] = (float*)list.plane(k, staging);
             yrt::dev_light_group_planes dp = {};
-            for (int g = 0; g < ngroups; g++) dp.group[g] = v[g];
-            dp.ambient = v[NP - 2], dp.beauty = v[NP - 1];
-            return dp;
+            for (int g = 0; g < YRT_LIGHT_GROUPS_MAX; g++) dp.group[g] = planes[g];
+            dp.ambient = planes[YRT_LIGHT_GROUPS_MAX], dp.beauty = planes[YRT_LIGHT_GROUPS_MAX + 1];
+            return yrt::launch_render_wavefront_light_groups(*s->ds, a, group_of, ngroups, dp, s->counters,
+                                                             p->algorithm == YRT_ALGO_WAVEFRONT, st);
         };
-        if (mem == YRT_MEM_DEVICE || r.tw <= 0 || r.th <= 0) {
-            // (an empty window launches nothing but the counters' memset: the planes are not touched)
-            hip_check(yrt::launch_render_wavefront_light_groups(*s->ds, a, group_of, ngroups, planes_of(host), s->counters,
-                                                                packet, st),
-                      "light groups render launch");
-            return YRT_OK;
-        }
-        // host planes: device staging of their own (the handle's scratch stays yrt_render's),
-        // copied back and released
-        const size_t bytes = (size_t)a.out_stride * r.th * 16;
-        struct staging {
-            void* p = nullptr;
-            ~staging() {
-                if (p) (void)hipFree(p);
-            }
-        } stage;
-        size_t used = 0;
-        for (int k = 0; k < NP; k++) used += host[k] ? 1 : 0;
-        hip_check(hipMalloc(&stage.p, bytes * used), "hipMalloc(light group staging)");
-        float* dev[NP] = {};
-        used = 0;
-        for (int k = 0; k < NP; k++)
-            if (host[k]) dev[k] = (float*)((char*)stage.p + bytes * used++);
-        // padding columns (out_stride > tile_w) keep the caller's bytes: they are staged too
-        if (a.out_stride > r.tw)
-            for (int k = 0; k < NP; k++)
-                if (host[k]) hip_check(hipMemcpyAsync(dev[k], host[k], bytes, hipMemcpyHostToDevice, st), "hipMemcpyAsync");
-        hipError_t e = hipSuccess;
-        try {
-            e = yrt::launch_render_wavefront_light_groups(*s->ds, a, group_of, ngroups, planes_of(dev), s->counters, packet,
-                                                          st);
-        } catch (...) {
-            (void)hipStreamSynchronize(st);  // the staging is released only after the stream has drained
-            throw;
-        }
-        for (int k = 0; k < NP && e == hipSuccess; k++)
-            if (host[k]) e = hipMemcpyAsync(host[k], dev[k], bytes, hipMemcpyDeviceToHost, st);
-        const hipError_t e2 = hipStreamSynchronize(st);
-        hip_check(e, "light groups render");
-        hip_check(e2, "hipStreamSynchronize");
+        // (an empty window launches nothing but the counters' memset: the planes are not touched)
+        if (mem == YRT_MEM_DEVICE || r.tw <= 0 || r.th <= 0)
+            hip_check(launch(nullptr), "light groups render launch");
+        else
+            stage_host_planes(list, a.out_stride > r.tw, st, "hipMalloc(light group staging)", "light groups render",
+                              launch);
         return YRT_OK;
     });
 }
@@ -921,7 +801,7 @@ static int trace_impl(yrt_scene* s, const float* rays, int n, int any, unsigned 
     return guarded([&] {
         hipStream_t st = (hipStream_t)stream;
         hip_check(hipSetDevice(s->ds->device), "hipSetDevice");
-        hip_check(hipMemsetAsync(s->counters, 0, yrt::cnt_slots * yrt::cnt_count * sizeof(unsigned long long), st), "hipMemsetAsync");
+        zero_counters(s, st);
         s->last_stream = st;
         if (n == 0) return YRT_OK;
         if (mem == YRT_MEM_DEVICE) {
@@ -986,8 +866,7 @@ int yrt_shade_rays(yrt_scene* s, const yrt_render_params* p, const float* rays, 
         hipStream_t st = (hipStream_t)stream;
         hip_check(hipSetDevice(s->ds->device), "hipSetDevice");
         if (n == 0) {  // nothing is written; the counters read zero
-            hip_check(hipMemsetAsync(s->counters, 0, yrt::cnt_slots * yrt::cnt_count * sizeof(unsigned long long), st),
-                      "hipMemsetAsync");
+            zero_counters(s, st);
             s->ds->timer.reset(false);
             s->last_stream = st;
             return YRT_OK;
@@ -996,9 +875,7 @@ int yrt_shade_rays(yrt_scene* s, const yrt_render_params* p, const float* rays, 
             p->algorithm != YRT_ALGO_WAVEFRONT_LANE)
             throw std::invalid_argument("unknown algorithm");
         if (p->count_work != 0) throw yrt::unsupported_error("ray batches do not count work");
-        yrt::dev_render_args a = {};
-        for (int k = 0; k < 3; k++) a.amb[k] = p->ambient[k];
-        a.max_depth = p->max_depth > 0 ? p->max_depth : 16;
+        yrt::dev_render_args a = frame_args(s, *p, nullptr, true);
         a.samples = 1;
         if (p->algorithm == YRT_ALGO_MEGAKERNEL && s->ds->reflective && a.max_depth > yrt::megakernel_max_depth)
             throw yrt::unsupported_error("the megakernel keeps " + std::to_string(yrt::megakernel_max_depth) +
@@ -1012,11 +889,10 @@ int yrt_shade_rays(yrt_scene* s, const yrt_render_params* p, const float* rays, 
             d_rays = (const float*)base;
             d_out = base + ((rb + 255) & ~(size_t)255);
         }
-        if (!(p->timing == 2 && s->ds->timer.on)) s->ds->timer.reset(p->timing != 0);
+        start_timer(s, *p);
         s->last_stream = st;
         if (p->algorithm == YRT_ALGO_MEGAKERNEL) {
-            hip_check(hipMemsetAsync(s->counters, 0, yrt::cnt_slots * yrt::cnt_count * sizeof(unsigned long long), st),
-                      "hipMemsetAsync");
+            zero_counters(s, st);
             hip_check(yrt::launch_shade_rays(*s->ds, a, d_rays, n, d_out, s->counters, st), "shade_rays launch");
         } else {
             hip_check(yrt::launch_shade_rays_wavefront(*s->ds, a, d_rays, n, d_out, s->counters,

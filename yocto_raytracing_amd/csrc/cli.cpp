@@ -62,54 +62,21 @@ int parse_int(const char* s, const char* opt) {
     return (int)v;
 }
 
+// the names of --aov, --mattes and --passes, in the order of YRT_AOV_*, YRT_MATTE_* and YRT_PASS_*
 const char* const aov_names[YRT_AOV_COUNT] = {"depth", "position", "normal", "texcoord", "albedo", "ids"};
-
-// --aov's comma-separated names as the YRT_AOV_* bit mask
-unsigned parse_aovs(const std::string& list) {
-    unsigned mask = 0;
-    for (size_t at = 0; at <= list.size();) {
-        size_t end = list.find(',', at);
-        if (end == std::string::npos) end = list.size();
-        const std::string name = list.substr(at, end - at);
-        int k = 0;
-        while (k < YRT_AOV_COUNT && name != aov_names[k]) k++;
-        if (k == YRT_AOV_COUNT) usage(("unknown --aov " + name).c_str());
-        mask |= 1u << k;
-        at = end + 1;
-    }
-    return mask;
-}
-
 const char* const matte_names[YRT_MATTE_KEY_COUNT] = {"instance", "material", "shape"};
-
-// --mattes' comma-separated key names as the YRT_MATTE_* bit mask
-unsigned parse_mattes(const std::string& list) {
-    unsigned mask = 0;
-    for (size_t at = 0; at <= list.size();) {
-        size_t end = list.find(',', at);
-        if (end == std::string::npos) end = list.size();
-        const std::string name = list.substr(at, end - at);
-        int k = 0;
-        while (k < YRT_MATTE_KEY_COUNT && name != matte_names[k]) k++;
-        if (k == YRT_MATTE_KEY_COUNT) usage(("unknown --mattes " + name).c_str());
-        mask |= 1u << k;
-        at = end + 1;
-    }
-    return mask;
-}
-
 const char* const pass_names[YRT_PASS_COUNT] = {"direct", "diffuse", "specular", "reflection", "ambient"};
 
-// --passes' comma-separated names as the YRT_PASS_* bit mask
-unsigned parse_passes(const std::string& list) {
+// option `opt`'s comma-separated names as the bit mask of their places in `names`
+unsigned parse_names(const std::string& list, const char* const* names, int count, const char* opt) {
     unsigned mask = 0;
     for (size_t at = 0; at <= list.size();) {
         size_t end = list.find(',', at);
         if (end == std::string::npos) end = list.size();
         const std::string name = list.substr(at, end - at);
         int k = 0;
-        while (k < YRT_PASS_COUNT && name != pass_names[k]) k++;
-        if (k == YRT_PASS_COUNT) usage(("unknown --passes " + name).c_str());
+        while (k < count && name != names[k]) k++;
+        if (k == count) usage((std::string("unknown ") + opt + " " + name).c_str());
         mask |= 1u << k;
         at = end + 1;
     }
@@ -183,9 +150,9 @@ int main(int argc, char** argv) {
             else if (n == "wavefront_lane") algorithm = YRT_ALGO_WAVEFRONT_LANE;
             else usage("unknown --algorithm");
         } else if (a == "--time") timing = true;
-        else if (a == "--aov") aovs = parse_aovs(val());
-        else if (a == "--passes") passes = parse_passes(val());
-        else if (a == "--mattes") mattes = parse_mattes(val());
+        else if (a == "--aov") aovs = parse_names(val(), aov_names, YRT_AOV_COUNT, "--aov");
+        else if (a == "--passes") passes = parse_names(val(), pass_names, YRT_PASS_COUNT, "--passes");
+        else if (a == "--mattes") mattes = parse_names(val(), matte_names, YRT_MATTE_KEY_COUNT, "--mattes");
         else if (a == "--matte-ranks") matte_ranks = parse_int(val(), "--matte-ranks");
         else if (a == "--light-groups") light_groups = parse_light_groups(val()), groups = true;
         else if (a == "-h" || a == "--help") usage(nullptr);

@@ -1,7 +1,7 @@
 // matte_args.h -- the host-side argument handling of yrt_render_mattes (capi.cpp): which
-// arguments are refused, and where each requested plane lies in the device staging of a call
-// with host planes. Plain C++ without the HIP runtime, so that it also builds into a
-// stand-alone program under the host sanitizers (tools/check_matte_args.cpp).
+// arguments are refused (where each requested plane lies in the staging of a call with host
+// planes: plane_staging.h). Plain C++ without the HIP runtime, so that it also builds into a
+// stand-alone program under the host sanitizers (tools/check_plane_staging.cpp).
 #pragma once
 
 #include <stddef.h>
@@ -20,31 +20,6 @@ inline const char* matte_args_error(unsigned key_mask, int layers, const yrt_mat
         for (int l = 0; l < layers; l++)
             if ((key_mask >> k & 1) && (!out->ids[k][l] || !out->coverage[k][l])) return "a requested matte plane is null";
     return nullptr;
-}
-
-// host planes: the requested planes in one device allocation, plane after plane
-struct matte_staging {
-    struct item {
-        void* host;     // the caller's plane
-        size_t offset;  // its place in the staging, in bytes
-        int key, layer, coverage;
-    };
-    item items[2 * YRT_MATTE_KEY_COUNT * YRT_MATTE_LAYERS_MAX];
-    int count = 0;
-    size_t bytes = 0;  // of the whole staging
-};
-
-inline matte_staging matte_stage_layout(unsigned key_mask, int layers, const yrt_matte_planes& out, size_t plane_bytes) {
-    matte_staging s;
-    for (int k = 0; k < YRT_MATTE_KEY_COUNT; k++) {
-        if (!(key_mask >> k & 1)) continue;
-        for (int l = 0; l < layers; l++)
-            for (int c = 0; c < 2; c++) {
-                s.items[s.count++] = {c ? (void*)out.coverage[k][l] : (void*)out.ids[k][l], s.bytes, k, l, c};
-                s.bytes += plane_bytes;
-            }
-    }
-    return s;
 }
 
 }  // namespace yrt
