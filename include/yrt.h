@@ -426,6 +426,49 @@ int yrt_scene_matte_dropped(yrt_scene* ds, unsigned long long dropped[YRT_MATTE_
  * NULL (both NULL: the count only), else the first min(n, cap) entries are written */
 int yrt_host_scene_instances(const yrt_host_scene* hs, int* shape, int* material, int cap, int* n);
 
+/* ---- adaptive supersampling: refine only the pixels that show contrast ----
+ * yrt_render spends s*s camera samples on every pixel. This call samples the frame at b*b per
+ * pixel and supersamples only where neighbouring pixels differ (Whitted's adaptive
+ * supersampling). With s = p->samples and b = base_samples, 1 <= b <= s, and every other field
+ * of `p` meaning what it means in yrt_render:
+ *   1. B is what yrt_render writes for `p` with samples = b, over the window grown by one pixel
+ *      on every side and clipped to the image (the apron; it goes to scratch, never to `out`).
+ *   2. An image pixel P of the window is flagged iff a pixel Q of the image with
+ *      max(|Px-Qx|, |Py-Qy|) == 1 and a channel c of r, g, b exist with
+ *      fabsf(B[P].c - B[Q].c) > threshold: float32 arithmetic, an IEEE comparison (false on NaN),
+ *      "exists", not "max of". Neighbours are pixels of the image, not of the window: a window's
+ *      result is the crop of the whole frame's, bit for bit.
+ *   3. A flagged pixel receives exactly yrt_render's value for samples = s: its s*s camera rays
+ *      (raytrace.cpp:228-250, jj outer and ii inner), each shaded by shade(), summed in float32
+ *      in that order from +0 and divided by float(s*s), .w = 1.
+ *   4. `out` has yrt_render's window layout (padding columns keep the caller's bytes): a flagged
+ *      pixel its refined value, every other image pixel B, local rows past the image edge zeros.
+ *      `refined`, when not NULL, is one byte per pixel in the same layout and stride: 1 flagged,
+ *      0 not, padding untouched.
+ * So threshold = +inf gives yrt_render(samples = b); on a frame of at least 2 x 2 finite pixels
+ * threshold < 0 gives yrt_render(samples = s); and b == s gives that render at any threshold.
+ * A null handle, p, a or out, a NaN threshold, b outside [1, s] after defaulting, chunk_pixels
+ * < 0, a bad `mem` or a bad camera return YRT_ERR_INVALID_ARG before any device call.
+ * YRT_ALGO_MEGAKERNEL, count_work = 1 and a band interleave other than band = 1, band_stride =
+ * 1, band_offset = 0 (the apron needs contiguous rows) return YRT_ERR_UNSUPPORTED. The call
+ * waits once on the stream, for the flagged count (as a reflective render does for its level
+ * counts); after that a host `out` makes it synchronous and a device `out` (16-byte aligned) is
+ * stream-ordered. The tile-list mode and the LDS staging of the handle apply to the base render
+ * and cannot change a bit. yrt_last_stats reports the base render's counters plus the refined
+ * pixels': camera_samples == grown-window image pixels * b*b + flagged * s*s, and likewise rays,
+ * shadow_rays, shadow_rays_culled and depth_truncated. yrt_last_timings adds the refinement's
+ * phases to the base's, the flag kernel under YRT_PHASE_LISTS and the refined pixels' sums
+ * under YRT_PHASE_ACCUMULATE. */
+typedef struct yrt_adaptive_params {
+    int   base_samples;  /* samples per axis of the base frame; 0 -> 1 */
+    float threshold;     /* contrast above which a pixel is refined */
+    int   chunk_pixels;  /* refined pixels per shading batch; 0 -> sized to the workspace; never changes a bit of the result */
+} yrt_adaptive_params;
+int yrt_render_adaptive(yrt_scene* ds, const yrt_render_params* p, const yrt_adaptive_params* a,
+                        float* out, unsigned char* refined /* may be NULL */, int mem, void* stream);
+/* the pixels the last yrt_render_adaptive on the handle flagged (0 before any); synchronises */
+int yrt_scene_adaptive_refined(yrt_scene* ds, unsigned long long* pixels);
+
 #ifdef __cplusplus
 }
 #endif

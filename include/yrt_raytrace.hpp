@@ -153,6 +153,34 @@ inline image4f raytrace(const std::unique_ptr<scene>& scn, const vec3f& amb, int
     return img;
 }
 
+// raytrace with adaptive supersampling (yrt_render_adaptive; one GPU): base_samples per axis in
+// every pixel, `samples` per axis -- raytrace's value, bit for bit -- in the pixels whose base
+// colour differs from a neighbour's by more than `threshold` in a channel. `refined`, when given,
+// receives width * height bytes, 1 where a pixel was refined.
+inline image4f raytrace_adaptive(const std::unique_ptr<scene>& scn, const vec3f& amb, int resolution, int samples,
+                                 float threshold, int base_samples = 1, std::vector<unsigned char>* refined = nullptr) {
+    yrt_scene* ds = scn->on_device();
+    yrt_render_params p = scn->params;
+    p.ambient[0] = amb.x, p.ambient[1] = amb.y, p.ambient[2] = amb.z;
+    p.resolution = resolution;
+    p.samples = samples;
+    int w = 0, h = 0;
+    check(yrt_image_size(ds, &p, &w, &h), "raytrace_adaptive");
+    image4f img(w, h);
+    if (refined) refined->assign((size_t)w * h, 0);
+    const yrt_adaptive_params a = {base_samples, threshold, 0};
+    check(yrt_render_adaptive(ds, &p, &a, &img.pixels[0].x, refined ? refined->data() : nullptr, YRT_MEM_HOST, nullptr),
+          "raytrace_adaptive");
+    return img;
+}
+
+// the pixels the last raytrace_adaptive refined
+inline unsigned long long adaptive_refined(const std::unique_ptr<scene>& scn) {
+    unsigned long long n = 0;
+    check(yrt_scene_adaptive_refined(scn->on_device(), &n), "adaptive_refined");
+    return n;
+}
+
 // counters of the last raytrace (summed over the GPUs when gpus > 1)
 inline yrt_stats last_stats(const std::unique_ptr<scene>& scn) {
     yrt_stats st{};

@@ -6,8 +6,8 @@
 //     clang++ $CXXFLAGS tools/check_plane_staging.cpp -o check_plane_staging && ./check_plane_staging
 //
 // It walks every matte key mask, layer count and mem, accepted and refused, every AOV mask,
-// every pass mask with and without a beauty, and 1 to 8 light groups with and without ambient
-// and beauty. For each accepted set it does what the entry point does with host planes: lays
+// every pass mask with and without a beauty, 1 to 8 light groups with and without ambient
+// and beauty, and yrt_render_adaptive's image with and without its byte mask. For each accepted set it does what the entry point does with host planes: lays
 // the requested planes out in one staging buffer, copies the caller's bytes in, fills every
 // staged plane, copies back, and checks that exactly the requested planes changed, each with its
 // own plane's contents, and that nothing was written past an end. No GPU and no HIP runtime:
@@ -171,6 +171,43 @@ void check_light_groups() {
         }
 }
 
+// yrt_render_adaptive: the image (slot 0, 16 B per pixel), then the byte mask when given (slot 1,
+// 1 B per pixel of the same rows and stride): two planes of different sizes in one staging
+void check_adaptive() {
+    const size_t pixels = (size_t)stride * h;
+    for (int with_mask = 0; with_mask < 2; with_mask++) {
+        std::vector<float> img(pixels * 4, (float)marker);
+        std::vector<unsigned char> mask(pixels, (unsigned char)marker);
+        const yrt::plane_list lay = yrt::adaptive_plane_list(img.data(), with_mask ? mask.data() : nullptr, pixels);
+        expect(lay.count == 1 + with_mask && lay.bytes == pixels * 16 + (with_mask ? pixels : 0),
+               "the image and the mask in one staging", 0, with_mask);
+        expect(lay.items[0].slot == 0 && lay.items[0].offset == 0 && lay.items[0].bytes == pixels * 16,
+               "the image leads", 0, with_mask);
+        if (with_mask)
+            expect(lay.items[1].slot == 1 && lay.items[1].offset == pixels * 16 && lay.items[1].bytes == pixels,
+                   "the mask follows the image, one byte per pixel", 0, with_mask);
+        std::vector<char> stage(lay.bytes);
+        for (int k = 0; k < lay.count; k++) memcpy(lay.plane(k, stage.data()), lay.items[k].host, lay.items[k].bytes);
+        for (int y = 0; y < h; y++)
+            for (int x = 0; x < w; x++) {
+                const float px[4] = {(float)y, (float)x, 0.0f, 1.0f};
+                memcpy((char*)lay.plane(0, stage.data()) + ((size_t)y * stride + x) * 16, px, 16);
+                if (with_mask) ((unsigned char*)lay.plane(1, stage.data()))[(size_t)y * stride + x] = (unsigned char)(y ^ x);
+            }
+        for (int k = 0; k < lay.count; k++) memcpy(lay.items[k].host, lay.plane(k, stage.data()), lay.items[k].bytes);
+        bool own = true, padding = true;
+        for (int y = 0; y < h; y++)
+            for (int x = 0; x < stride; x++) {
+                const float* px = &img[((size_t)y * stride + x) * 4];
+                const unsigned char m = mask[(size_t)y * stride + x];
+                if (x < w) own = own && px[0] == (float)y && px[1] == (float)x && (m == (with_mask ? (y ^ x) : marker));
+                else padding = padding && px[0] == (float)marker && px[3] == (float)marker && m == marker;
+            }
+        expect(own, "the image and the mask came back to their owners", 0, with_mask);
+        expect(padding, "padding columns keep the caller's bytes", 0, with_mask);
+    }
+}
+
 }  // namespace
 
 int main() {
@@ -178,6 +215,7 @@ int main() {
     check_aovs();
     check_passes();
     check_light_groups();
+    check_adaptive();
     if (failures) return 1;
     printf("ok\n");
     return 0;

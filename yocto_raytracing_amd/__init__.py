@@ -23,7 +23,7 @@ from . import _native as N
 from ._native import RenderParams, Stats, YrtError, check
 
 __all__ = [
-    "Scene", "DeviceScene", "load_scene", "build_bvh", "raytrace", "render_aovs", "render_passes", "render_light_groups",
+    "Scene", "DeviceScene", "load_scene", "build_bvh", "raytrace", "raytrace_adaptive", "render_aovs", "render_passes", "render_light_groups",
     "render_mattes", "matte", "intersect_first",
     "intersect_any", "shade_rays", "tonemap", "save_hdr_or_ldr", "render_params", "device_count", "YrtError",
 ]
@@ -312,6 +312,24 @@ class DeviceScene:
         check(N.lib.yrt_shade_rays(self._h, C.byref(params), C.c_void_p(rays_ptr), int(n), C.c_void_p(out_ptr),
                                    _mem(device_memory), C.c_void_p(stream or 0)), "yrt_shade_rays")
 
+    def render_adaptive_into(self, params: RenderParams, out_ptr: int, threshold: float, base_samples: int = 1,
+                             refined_ptr: Optional[int] = None, chunk_pixels: int = 0, device_memory: bool = True,
+                             stream: Optional[int] = None) -> None:
+        """Launch raytrace() with adaptive supersampling (yrt_render_adaptive) into a caller buffer
+        in render_into's layout: `base_samples` per axis in every pixel, `params.samples` per axis
+        in the pixels whose base colour differs from a neighbour's by more than `threshold` in a
+        channel. `refined_ptr`, when given, receives one byte per pixel, 1 where refined."""
+        ap = N.AdaptiveParams(int(base_samples), float(threshold), int(chunk_pixels))
+        check(N.lib.yrt_render_adaptive(self._h, C.byref(params), C.byref(ap), C.c_void_p(out_ptr),
+                                        C.c_void_p(refined_ptr or 0), _mem(device_memory), C.c_void_p(stream or 0)),
+              "yrt_render_adaptive")
+
+    def adaptive_refined(self) -> int:
+        """the pixels the last render_adaptive_into refined; waits for that call"""
+        n = C.c_ulonglong()
+        check(N.lib.yrt_scene_adaptive_refined(self._h, C.byref(n)), "yrt_scene_adaptive_refined")
+        return int(n.value)
+
     def last_timings(self) -> dict:
         """per-phase GPU ms of the last render with timing=True: {phase: (ms, launches)}"""
         t = N.Timings()
@@ -479,6 +497,31 @@ def raytrace(scn, amb: Sequence[float] = (0.1, 0.1, 0.1), resolution: int = 720,
     if return_stats:
         return img, ds.last_stats()
     return img
+
+
+def raytrace_adaptive(scn, amb: Sequence[float] = (0.1, 0.1, 0.1), resolution: int = 720, samples: int = 1, *,
+                      threshold: float, base_samples: int = 1, width: int = 0, window=None, max_depth: int = 16,
+                      algorithm: str = "wavefront", chunk_pixels: int = 0, return_mask: bool = False,
+                      return_stats: bool = False):
+    """raytrace with adaptive supersampling: every pixel gets base_samples x base_samples camera
+    samples, and a pixel whose base colour differs from one of its eight neighbours' by more than
+    `threshold` in r, g or b gets raytrace's value at samples x samples instead, bit for bit.
+    Returns the (H, W, 4) float32 image; with `return_mask` also the (H, W) uint8 mask of the
+    refined pixels, with `return_stats` also last_stats() plus "refined_pixels". `chunk_pixels`
+    (0: chosen by the library) sizes the shading batches and never changes a bit. `scn` is a
+    Scene or a DeviceScene, as for raytrace."""
+    ds = _device_scene(scn)
+    p = render_params(amb, resolution, samples, width=width, max_depth=max_depth, window=window, algorithm=algorithm)
+    h, w = _window_shape(ds, p, window)
+    img = np.zeros((h, w, 4), np.float32)
+    mask = np.zeros((h, w), np.uint8) if return_mask else None
+    ds.render_adaptive_into(p, img.ctypes.data, threshold, base_samples,
+                            refined_ptr=mask.ctypes.data if return_mask else None, chunk_pixels=chunk_pixels,
+                            device_memory=False)
+    out = (img,) + ((mask,) if return_mask else ())
+    if return_stats:
+        out += (dict(ds.last_stats(), refined_pixels=ds.adaptive_refined()),)
+    return out if len(out) > 1 else img
 
 
 def render_aovs(scn, resolution: int = 720, samples: int = 1, *, aovs: Sequence[str] = tuple(N.AOVS),

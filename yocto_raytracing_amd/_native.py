@@ -126,6 +126,12 @@ class MattePlanes(C.Structure):
                 ("coverage", C.c_void_p * YRT_MATTE_LAYERS_MAX * YRT_MATTE_KEY_COUNT)]
 
 
+# yrt_render_adaptive: the base frame's samples per axis (0: 1), the contrast threshold, the
+# refined pixels per shading batch (0: sized by the library)
+class AdaptiveParams(C.Structure):
+    _fields_ = [("base_samples", C.c_int), ("threshold", C.c_float), ("chunk_pixels", C.c_int)]
+
+
 _vp = C.c_void_p
 _ip =C.POINTER(C.c_int)
 _sig = {
@@ -183,6 +189,8 @@ _sig = {
                                     _vp]),
     "yrt_scene_matte_dropped": (C.c_int, [_vp, C.POINTER(C.c_ulonglong)]),
     "yrt_host_scene_instances": (C.c_int, [_vp, _ip, _ip, C.c_int, _ip]),
+    "yrt_render_adaptive": (C.c_int, [_vp, C.POINTER(RenderParams), C.POINTER(AdaptiveParams), _vp, _vp, C.c_int, _vp]),
+    "yrt_scene_adaptive_refined": (C.c_int, [_vp, C.POINTER(C.c_ulonglong)]),
 }
 EXPORTS = tuple(_sig)
 

@@ -169,11 +169,11 @@ void stage_host_planes(const yrt::plane_list& list, bool padded, hipStream_t st,
     hipError_t e = hipSuccess;
     try {
         for (int k = 0; k < list.count && padded; k++)
-            hip_check(hipMemcpyAsync(list.plane(k, stage), list.items[k].host, list.plane_bytes, hipMemcpyHostToDevice, st),
+            hip_check(hipMemcpyAsync(list.plane(k, stage), list.items[k].host, list.items[k].bytes, hipMemcpyHostToDevice, st),
                       "hipMemcpyAsync");
         e = launch(stage);
         for (int k = 0; k < list.count && e == hipSuccess; k++)
-            e = hipMemcpyAsync(list.items[k].host, list.plane(k, stage), list.plane_bytes, hipMemcpyDeviceToHost, st);
+            e = hipMemcpyAsync(list.items[k].host, list.plane(k, stage), list.items[k].bytes, hipMemcpyDeviceToHost, st);
     } catch (...) {
         (void)hipStreamSynchronize(st);
         (void)hipFree(stage);
@@ -903,6 +903,63 @@ int yrt_shade_rays(yrt_scene* s, const yrt_render_params* p, const float* rays, 
             hip_check(hipMemcpyAsync(out, d_out, ob, hipMemcpyDeviceToHost, st), "hipMemcpyAsync");
             hip_check(hipStreamSynchronize(st), "hipStreamSynchronize");
         }
+        return YRT_OK;
+    });
+}
+
+int yrt_render_adaptive(yrt_scene* s, const yrt_render_params* p, const yrt_adaptive_params* ap, float* out,
+                        unsigned char* refined, int mem, void* stream) {
+    // (before any device call, and before the handle is looked at)
+    const int b = ap && ap->base_samples == 0 ? 1 : ap ? ap->base_samples : 0;
+    const char* bad = !s                                           ? "yrt_render_adaptive: null scene handle"
+                      : !p                                         ? "yrt_render_adaptive: null params"
+                      : !ap                                        ? "yrt_render_adaptive: null adaptive params"
+                      : !out                                       ? "yrt_render_adaptive: null out"
+                      : std::isnan(ap->threshold)                  ? "yrt_render_adaptive: the threshold is NaN"
+                      : b < 1 || b > p->samples                    ? "yrt_render_adaptive: base_samples outside [1, samples]"
+                      : ap->chunk_pixels < 0                       ? "yrt_render_adaptive: chunk_pixels < 0"
+                      : mem != YRT_MEM_HOST && mem != YRT_MEM_DEVICE ? "yrt_render_adaptive: mem is not YRT_MEM_*"
+                      : p->camera < 0                              ? "yrt_render_adaptive: camera index out of range"
+                                                                   : nullptr;
+    if (bad) {
+        g_last_error = bad;
+        return YRT_ERR_INVALID_ARG;
+    }
+    return guarded([&] {
+        auto r = resolve(*s->ds, *p);
+        const yrt::dev_render_args a = frame_args(s, *p, &r, true);  // (its refusal comes before any device call)
+        if (p->algorithm == YRT_ALGO_MEGAKERNEL)
+            throw yrt::unsupported_error("adaptive supersampling runs in the wavefront algorithms");
+        if (p->algorithm != YRT_ALGO_WAVEFRONT && p->algorithm != YRT_ALGO_WAVEFRONT_LANE)
+            throw std::invalid_argument("unknown algorithm");
+        if (p->count_work != 0) throw yrt::unsupported_error("adaptive supersampling does not count work");
+        if (p->band != 1 || p->band_stride != 1 || p->band_offset != 0)
+            throw yrt::unsupported_error("adaptive supersampling takes contiguous rows: its apron has no band interleave");
+        hipStream_t st = (hipStream_t)stream;
+        hip_check(hipSetDevice(s->ds->device), "hipSetDevice");
+        start_timer(s, *p);
+        s->last_stream = st;
+        const yrt::plane_list list = yrt::adaptive_plane_list(out, refined, (size_t)a.out_stride * r.th);
+        auto launch = [&](void* staging) {
+            return yrt::launch_render_adaptive(*s->ds, a, b, ap->threshold, ap->chunk_pixels, list.plane(0, staging),
+                                               refined ? (unsigned char*)list.plane(1, staging) : nullptr, s->counters,
+                                               p->algorithm == YRT_ALGO_WAVEFRONT, st);
+        };
+        // (an empty window launches nothing but the counters' memset: the planes are not touched)
+        if (mem == YRT_MEM_DEVICE || r.tw <= 0 || r.th <= 0)
+            hip_check(launch(nullptr), "adaptive render launch");
+        else
+            stage_host_planes(list, a.out_stride > r.tw, st, "hipMalloc(adaptive staging)", "adaptive render", launch);
+        return YRT_OK;
+    });
+}
+
+int yrt_scene_adaptive_refined(yrt_scene* s, unsigned long long* pixels) {
+    if (!s || !pixels) return YRT_ERR_INVALID_ARG;
+    return guarded([&] {
+        hip_check(hipSetDevice(s->ds->device), "hipSetDevice");
+        hip_check(hipStreamSynchronize(s->last_stream), "hipStreamSynchronize");
+        *pixels = s->ds->adaptive_refined;
         return YRT_OK;
     });
 }

@@ -10,7 +10,8 @@
 // image's lighting split, from the same render, as .npy files beside it), --light-groups LIST
 // (one plane per group of lights and the ambient plane, from the same render, as .npy files),
 // --mattes LIST with --matte-ranks 4|8 (ID mattes: per key the ranked ids covering each pixel and
-// their coverages, from one pass, as .npy files).
+// their coverages, from one pass, as .npy files), --adaptive THRESHOLD with --base-samples N (the
+// image with adaptive supersampling, and the refined pixels' mask as a .npy file).
 #include <algorithm>
 #include <chrono>
 #include <cstdio>
@@ -51,7 +52,12 @@ namespace {
             "                       instance,material,shape: per pixel the ids covering it, ranked by their\n"
             "                       share of the pixel's samples (-1 and 0 in unused ranks), from one pass\n"
             "                       (one GPU)\n"
-            "  --matte-ranks N      ranks per pixel and key of --mattes, 4 or 8 [4]\n");
+            "  --matte-ranks N      ranks per pixel and key of --mattes, 4 or 8 [4]\n"
+            "  --adaptive F         adaptive supersampling: --base-samples per axis in every pixel, -s per axis\n"
+            "                       only where a pixel differs from a neighbour by more than F in a channel;\n"
+            "                       prints the refined pixels and also writes OUT.refined.npy, (H, W) uint8\n"
+            "                       (one GPU, a wavefront algorithm)\n"
+            "  --base-samples N     samples per axis of --adaptive's base frame [1]\n");
     exit(msg ? 1 : 0);
 }
 
@@ -101,18 +107,19 @@ std::vector<int> parse_light_groups(const std::string& list) {
     return groups;
 }
 
-// a (h, w, channels) array of 4-byte elements as a NumPy format 1.0 file, C order: the magic,
-// the version, the header dict's length, the dict padded with spaces so that the data starts on
-// a multiple of 64 bytes, a newline, the data
+// a (h, w, channels) array of 4-byte elements -- or, with channels = 0, a (h, w) array of bytes --
+// as a NumPy format 1.0 file, C order: the magic, the version, the header dict's length, the
+// dict padded with spaces so that the data starts on a multiple of 64 bytes, a newline, the data
 void save_npy(const std::string& path, const void* data, int w, int h, const char* descr, int channels = 4) {
     std::string dict = std::string("{'descr': '") + descr + "', 'fortran_order': False, 'shape': (" +
-                       std::to_string(h) + ", " + std::to_string(w) + ", " + std::to_string(channels) + "), }";
+                       std::to_string(h) + ", " + std::to_string(w) +
+                       (channels ? ", " + std::to_string(channels) : std::string()) + "), }";
     while ((10 + dict.size() + 1) % 64) dict += ' ';
     dict += '\n';
     const unsigned char head[10] = {0x93, 'N', 'U', 'M', 'P', 'Y', 1, 0, (unsigned char)(dict.size() & 0xff),
                                     (unsigned char)(dict.size() >> 8)};
     FILE* f = fopen(path.c_str(), "wb");
-    const size_t bytes = (size_t)w * h * 4 * channels;
+    const size_t bytes = channels ? (size_t)w * h * 4 * channels : (size_t)w * h;
     const bool ok = f && fwrite(head, 1, sizeof head, f) == sizeof head &&
                     fwrite(dict.data(), 1, dict.size(), f) == dict.size() && fwrite(data, 1, bytes, f) == bytes;
     if ((f && fclose(f) != 0) || !ok) throw yrt_cpp::error(YRT_ERR_IO, "cannot write " + path);
@@ -127,7 +134,9 @@ int main(int argc, char** argv) {
     unsigned aovs = 0, passes = 0, mattes = 0;
     int matte_ranks = 4;
     std::vector<int> light_groups;
-    bool groups = false;
+    bool groups = false, adaptive = false;
+    float threshold = 0.0f;
+    int base_samples = 1;
     std::string out = "out.png", scenein;
     for (int k = 1; k < argc; k++) {
         std::string a = argv[k];
@@ -155,6 +164,13 @@ int main(int argc, char** argv) {
         else if (a == "--mattes") mattes = parse_names(val(), matte_names, YRT_MATTE_KEY_COUNT, "--mattes");
         else if (a == "--matte-ranks") matte_ranks = parse_int(val(), "--matte-ranks");
         else if (a == "--light-groups") light_groups = parse_light_groups(val()), groups = true;
+        else if (a == "--adaptive") {
+            const char* v = val();
+            char* end = nullptr;
+            threshold = strtof(v, &end);
+            if (!*v || *end || threshold != threshold) usage("bad value for --adaptive");
+            adaptive = true;
+        } else if (a == "--base-samples") base_samples = parse_int(val(), "--base-samples");
         else if (a == "-h" || a == "--help") usage(nullptr);
         else if (!a.empty() && a[0] == '-') usage(("unknown option " + a).c_str());
         else if (scenein.empty()) scenein = a;
@@ -171,6 +187,11 @@ int main(int argc, char** argv) {
     if (groups && algorithm == YRT_ALGO_MEGAKERNEL)
         usage("--light-groups needs a wavefront algorithm, not --algorithm megakernel");
     if (groups && passes) usage("--light-groups and --passes are renders of their own: give one of them");
+    if (adaptive && gpus > 1) usage("--adaptive renders on one GPU (--gpus 1)");
+    if (adaptive && algorithm == YRT_ALGO_MEGAKERNEL)
+        usage("--adaptive needs a wavefront algorithm, not --algorithm megakernel");
+    if (adaptive && (passes || groups)) usage("--adaptive renders the image alone: not with --passes or --light-groups");
+    if (adaptive && (base_samples < 1 || base_samples > samples)) usage("--base-samples must be from 1 to -s");
     try {
         printf("loading scene %s\n", scenein.c_str());
         auto scn = yrt_cpp::load_scene(scenein);
@@ -199,6 +220,7 @@ int main(int argc, char** argv) {
         std::vector<std::vector<float>> group_data(groups ? ngroups + 1 : 0);  // the groups, then the ambient
         auto t0 = std::chrono::steady_clock::now();
         yrt_cpp::image4f hdr;
+        std::vector<unsigned char> refined;  // --adaptive's mask
         if (passes) {
             // one render: the image and its passes in host memory
             yrt_render_params p = scn->params;
@@ -234,6 +256,11 @@ int main(int argc, char** argv) {
             yrt_cpp::check(yrt_render_light_groups(scn->on_device(), &p, light_groups.empty() ? &none : light_groups.data(),
                                                    (int)light_groups.size(), ngroups, &lp, YRT_MEM_HOST, nullptr),
                            "render_light_groups");
+        } else if (adaptive) {
+            hdr = yrt_cpp::raytrace_adaptive(scn, {amb, amb, amb}, resolution, samples, threshold, base_samples, &refined);
+            const unsigned long long n = yrt_cpp::adaptive_refined(scn);
+            printf("adaptive: refined %llu of %llu pixels (%.1f %%)\n", n, (unsigned long long)refined.size(),
+                   refined.empty() ? 0.0 : 100.0 * (double)n / (double)refined.size());
         } else
             hdr = yrt_cpp::raytrace(scn, {amb, amb, amb}, resolution, samples);
         auto t1 = std::chrono::steady_clock::now();
@@ -253,6 +280,7 @@ int main(int argc, char** argv) {
         for (size_t g = 0; g < group_data.size(); g++)
             save_npy(stem + (g + 1 < group_data.size() ? ".group" + std::to_string(g) : std::string(".ambient")) + ".npy",
                      group_data[g].data(), hdr.width, hdr.height, "<f4");
+        if (adaptive) save_npy(stem + ".refined.npy", refined.data(), hdr.width, hdr.height, "|u1", 0);
         if (aovs) {
             // the requested planes in host memory, each saved as <output without extension>.<name>.npy
             yrt_render_params p = scn->params;

@@ -1,5 +1,5 @@
 // plane_staging.h -- the caller's planes of one call of yrt_render_aovs, yrt_render_mattes,
-// yrt_render_passes or yrt_render_light_groups as one list, and where each lies in the device
+// yrt_render_passes, yrt_render_light_groups or yrt_render_adaptive as one list, and where each lies in the device
 // staging of a call with host planes (capi.cpp stage_host_planes). Plain C++ without the HIP
 // runtime, so that it also builds into a stand-alone program under the host sanitizers
 // (tools/check_plane_staging.cpp).
@@ -19,6 +19,7 @@ struct plane_list {
         void* host;     // the caller's plane
         size_t offset;  // its place in the staging, in bytes
         int slot;       // which plane of the entry point's struct it is (the *_plane_list below)
+        size_t bytes;   // the plane's size: plane_bytes, or what add_sized gave it
     };
     item items[capacity];
     int count = 0;
@@ -26,9 +27,12 @@ struct plane_list {
     size_t bytes = 0;  // of the whole staging
 
     explicit plane_list(size_t plane_bytes) : plane_bytes(plane_bytes) {}
-    void add(void* host, int slot) {
-        items[count++] = {host, bytes, slot};
-        bytes += plane_bytes;
+    void add(void* host, int slot) { add_sized(host, slot, plane_bytes); }
+    // a plane of another pixel size (yrt_render_adaptive's byte mask); such planes come last, so
+    // that the 16-byte pixels before them keep their alignment
+    void add_sized(void* host, int slot, size_t item_bytes) {
+        items[count++] = {host, bytes, slot, item_bytes};
+        bytes += item_bytes;
     }
     // the memory the kernels write for item k: in the staging, or without one the caller's plane
     void* plane(int k, void* staging) const { return staging ? (char*)staging + items[k].offset : items[k].host; }
@@ -75,6 +79,15 @@ inline plane_list light_group_plane_list(int ngroups, const yrt_light_group_plan
     for (int g = 0; g < ngroups; g++) l.add(out.group[g], g);
     if (out.ambient) l.add(out.ambient, YRT_LIGHT_GROUPS_MAX);
     if (out.beauty) l.add(out.beauty, YRT_LIGHT_GROUPS_MAX + 1);
+    return l;
+}
+
+// yrt_render_adaptive: the image, slot 0, then the byte mask when given, slot 1, of
+// pixels bytes (1 B per pixel of the same rows and stride)
+inline plane_list adaptive_plane_list(float* out, unsigned char* refined, size_t pixels) {
+    plane_list l(pixels * 16);
+    l.add(out, 0);
+    if (refined) l.add_sized(refined, 1, pixels);
     return l;
 }
 

@@ -383,3 +383,5 @@ hipError_t launch_tonemap(const float* rgba, int n, unsigned char* out, const to
 #include "aov.hip"
 // the ID-matte pass (k_matte, launch_mattes), on the AOV pass's tile geometry
 #include "mattes.hip"
+// adaptive supersampling (k_adaptive_*, launch_render_adaptive)
+#include "adaptive.hip"

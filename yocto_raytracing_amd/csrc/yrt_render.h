@@ -85,6 +85,17 @@ struct device_scene {
     // yrt_render_light_groups: the last call's table of lights sorted by plane, the source of
     // its copy to the device (wavefront.hip group_buffers::tab)
     std::vector<int> group_tab;
+    // yrt_render_adaptive (adaptive.hip), grown on demand like `work`: the frame scratch (the
+    // flagged count, the saved counter lines, the base frame with its apron, the flagged list)
+    // and a chunk's rays and colours; the flagged count on the host (pinned), copied back
+    // behind the flag kernel, and the last call's value of it
+    void* adaptive_frame = nullptr;
+    size_t adaptive_frame_bytes = 0;
+    void* adaptive_rays = nullptr;
+    size_t adaptive_rays_bytes = 0;
+    unsigned long long* adaptive_count_host = nullptr;
+    hipEvent_t adaptive_count_ev = nullptr;
+    unsigned long long adaptive_refined = 0;
     phase_timer timer;
 };
 
@@ -206,5 +217,19 @@ struct dev_light_group_planes {
 hipError_t launch_render_wavefront_light_groups(device_scene& ds, const dev_render_args& args, const int* group_of,
                                                 int ngroups, const dev_light_group_planes& out,
                                                 unsigned long long* counters, bool packet, hipStream_t stream);
+
+// adaptive supersampling (adaptive.hip, yrt_render_adaptive): args is the call's frame at its
+// full samples per axis (contiguous rows: band 1, stride 1, offset 0). The base frame at
+// base_samples per axis comes from launch_render_wavefront over the window grown by one pixel
+// (into scratch), k_adaptive_flag tests it against `threshold`, writes it to out_rgba, the byte
+// mask to `refined` (may be null; out's layout, 1 B per pixel) and the flagged pixels to a list,
+// and the flagged pixels are refined in chunks of chunk_pixels (0: as many as keep a chunk within
+// adaptive_chunk_rays rays) through launch_shade_rays_wavefront. Waits once on the stream, for
+// the flagged count (kept in ds.adaptive_refined). The counters are the base render's plus the
+// batches'; timings are added per phase.
+constexpr long long adaptive_chunk_rays = 1ll << 23;  // 48 B a ray (32 B ray + 16 B colour): 384 MiB
+hipError_t launch_render_adaptive(device_scene& ds, const dev_render_args& args, int base_samples, float threshold,
+                                  int chunk_pixels, void* out_rgba, unsigned char* refined,
+                                  unsigned long long* counters, bool packet, hipStream_t stream);
 
 }  // namespace yrt
