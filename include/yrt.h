@@ -469,6 +469,59 @@ int yrt_render_adaptive(yrt_scene* ds, const yrt_render_params* p, const yrt_ada
 /* the pixels the last yrt_render_adaptive on the handle flagged (0 before any); synchronises */
 int yrt_scene_adaptive_refined(yrt_scene* ds, unsigned long long* pixels);
 
+/* ---- ambient occlusion: cosine-weighted any-hit rays per camera sample ----
+ * Per pixel the share of the hemisphere above the camera hit that is open within `distance`.
+ * Over the beauty's sample grid (raytrace.cpp:228-250, jj outer, ii inner) each camera sample
+ * is answered by intersect_first, exactly as in yrt_render_aovs. A sample that misses
+ * contributes nothing. A sample that hits a shape of lines or points casts no ray and counts
+ * as K unoccluded rays (eval_pos of a point is the sphere's centre, eval_norm of a line its
+ * tangent: there is no hemisphere). A sample that hits a triangle casts K rays, all float32,
+ * evaluated left to right with no contraction:
+ *   1. p = eval_pos, n = eval_norm, d the camera ray's direction; if dot(n, d) > 0.0f then
+ *      n = -n (false on NaN); dot is a.x*b.x + a.y*b.y + a.z*b.z.
+ *   2. the basis (Duff et al., the sign taken so that +0 and -0 agree):
+ *      sg = (n.z >= 0.0f) ? 1.0f : -1.0f;  a = -1.0f / (sg + n.z);  b = n.x * n.y * a;
+ *      b1 = { 1.0f + sg * n.x * n.x * a, sg * b, -sg * n.x };  b2 = { b, sg + n.y * n.y * a, -n.y }.
+ *   3. r = ((i & 3) | (j & 3) << 2) ^ ((jj * s + ii) & 15) with i, j the pixel's image
+ *      coordinates (not the window's); (c, sn) = rots[r].
+ *   4. for k = 0 .. K-1 with (tx, ty, tz) = dirs[k]:  x = c*tx - sn*ty;  y = sn*tx + c*ty;
+ *      dir = (b1*x + b2*y) + n*tz componentwise; the ray {p, dir, bias, distance}, not
+ *      renormalised, is answered by intersect_any.
+ *   5. the sample's count is the number of its K rays that are not occluded.
+ * The tables are compile-time constants (yrt_ao_tables returns them): dirs[k] =
+ * (rr cos phi, rr sin phi, sqrt(1 - u1)) with u1 = halton_2(k+1), u2 = halton_3(k+1),
+ * rr = sqrt(u1), phi = 2 pi u2 -- cosine-weighted, so the plain count is the estimator, any
+ * prefix K is a usable set, and the smallest tz is 0.125; rots[r] = (cos t, sin t) with
+ * t = 2 pi bitrev4(r) / 16. Each value is computed in double and rounded once to float32.
+ * `out` has yrt_render's window layout (RGBA f32, out_stride, padding columns keep the
+ * caller's bytes, local rows past the image edge read as zeros). Per image pixel U is the sum
+ * of the sample counts (K per line or point hit), a = float(U) / float(K*s*s),
+ * w = float(hits) / float(s*s), and the pixel is {a, a, a, w}: .w is the depth AOV's .w bit
+ * for bit, 0 <= a <= w, and a / w is the pixel's ambient occlusion in [0, 1]. The result is a
+ * count: the same bits on every run. The fields of `p` are used and ignored exactly as in
+ * yrt_render_aovs (resolution, width, samples, camera, the window, the band interleave and
+ * out_stride are used); a window is the crop of the whole frame's result and band shards
+ * reassemble to it; an empty window or band writes nothing and counts nothing. A host `out`
+ * makes the call synchronous, a device `out` (16-byte aligned) is stream-ordered. The pass
+ * shares no state with yrt_render; the tile-list mode and the LDS staging do not apply.
+ * yrt_last_stats reports camera_samples == window image pixels * s*s, shadow_rays == K *
+ * (samples that hit a triangle), rays == camera_samples + shadow_rays, every other counter 0.
+ * A null handle, p, a or out, rays outside 1..64 after defaulting, a distance that is NaN or
+ * <= 0, a bias that is NaN, negative, infinite or >= distance, a bad `mem` or a bad camera
+ * index return YRT_ERR_INVALID_ARG before any device call. */
+#define YRT_AO_RAYS_MAX 64
+typedef struct yrt_ao_params {
+    int   rays;      /* K, occlusion rays per camera sample that hits a triangle; 0 -> 16; 1..64 */
+    float distance;  /* tmax of an occlusion ray; > 0; +inf is taken as FLT_MAX */
+    float bias;      /* tmin of an occlusion ray; finite, >= 0, < distance */
+} yrt_ao_params;
+void yrt_ao_params_default(yrt_ao_params* a);            /* 16, FLT_MAX, 0.01f (the shadow rays' tmin) */
+int  yrt_ao_tables(float dirs[64 * 3], float rots[16 * 2]); /* the two tables above, as the kernel reads them */
+int  yrt_render_ao(yrt_scene* ds, const yrt_render_params* p, const yrt_ao_params* a,
+                   float* out, int mem, void* stream);
+/* per shape its primitive kind: 0 triangles, 1 lines, 2 points, 3 empty; n always set; kind may be NULL */
+int  yrt_host_scene_shape_kinds(const yrt_host_scene* hs, int* kind, int cap, int* n);
+
 #ifdef __cplusplus
 }
 #endif

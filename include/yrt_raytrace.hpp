@@ -181,6 +181,23 @@ inline unsigned long long adaptive_refined(const std::unique_ptr<scene>& scn) {
     return n;
 }
 
+// the ambient occlusion plane (yrt_render_ao; one GPU) on raytrace's sample grid: per pixel
+// {a, a, a, w}, a the unoccluded share of `rays` cosine-weighted rays over [bias, distance] per
+// camera sample times the coverage w. The defaults are yrt_ao_params_default's.
+inline image4f render_ao(const std::unique_ptr<scene>& scn, int resolution, int samples, int rays = 16,
+                         float distance = 3.402823466e+38f, float bias = 0.01f) {
+    yrt_scene* ds = scn->on_device();
+    yrt_render_params p = scn->params;
+    p.resolution = resolution;
+    p.samples = samples;
+    int w = 0, h = 0;
+    check(yrt_image_size(ds, &p, &w, &h), "render_ao");
+    image4f img(w, h);
+    const yrt_ao_params a = {rays, distance, bias};
+    check(yrt_render_ao(ds, &p, &a, &img.pixels[0].x, YRT_MEM_HOST, nullptr), "render_ao");
+    return img;
+}
+
 // counters of the last raytrace (summed over the GPUs when gpus > 1)
 inline yrt_stats last_stats(const std::unique_ptr<scene>& scn) {
     yrt_stats st{};

@@ -24,7 +24,7 @@ from ._native import RenderParams, Stats, YrtError, check
 
 __all__ = [
     "Scene", "DeviceScene", "load_scene", "build_bvh", "raytrace", "raytrace_adaptive", "render_aovs", "render_passes", "render_light_groups",
-    "render_mattes", "matte", "intersect_first",
+    "render_mattes", "matte", "render_ao", "ao_tables", "intersect_first",
     "intersect_any", "shade_rays", "tonemap", "save_hdr_or_ldr", "render_params", "device_count", "YrtError",
 ]
 
@@ -152,6 +152,15 @@ class Scene:
         shp, mat = (C.c_int * max(n.value, 1))(), (C.c_int * max(n.value, 1))()
         check(N.lib.yrt_host_scene_instances(self._h, shp, mat, n.value, C.byref(n)), "yrt_host_scene_instances")
         return list(zip(shp[:n.value], mat[:n.value]))
+
+    def shape_kinds(self) -> list:
+        """the primitive kind of each shape, in scene order: 0 triangles, 1 lines, 2 points, 3
+        empty (the .w of render_aovs' "ids" indexes it; render_ao casts rays from triangles only)"""
+        n = C.c_int()
+        check(N.lib.yrt_host_scene_shape_kinds(self._h, None, 0, C.byref(n)), "yrt_host_scene_shape_kinds")
+        kind = (C.c_int * max(n.value, 1))()
+        check(N.lib.yrt_host_scene_shape_kinds(self._h, kind, n.value, C.byref(n)), "yrt_host_scene_shape_kinds")
+        return list(kind[:n.value])
 
     def image_size(self, resolution: int, camera: int = 0):
         w, h = C.c_int(), C.c_int()
@@ -329,6 +338,15 @@ class DeviceScene:
         n = C.c_ulonglong()
         check(N.lib.yrt_scene_adaptive_refined(self._h, C.byref(n)), "yrt_scene_adaptive_refined")
         return int(n.value)
+
+    def render_ao_into(self, params: RenderParams, out_ptr: int, rays: int = 16, distance: float = float("inf"),
+                       bias: float = 0.01, device_memory: bool = True, stream: Optional[int] = None) -> None:
+        """Launch the ambient occlusion pass (yrt_render_ao) into a caller buffer in render_into's
+        layout: per pixel {a, a, a, w}, a the unoccluded share of `rays` cosine-weighted rays
+        ([bias, distance]) per camera sample, premultiplied by the coverage w."""
+        ap = N.AoParams(int(rays), float(distance), float(bias))
+        check(N.lib.yrt_render_ao(self._h, C.byref(params), C.byref(ap), C.c_void_p(out_ptr), _mem(device_memory),
+                                  C.c_void_p(stream or 0)), "yrt_render_ao")
 
     def last_timings(self) -> dict:
         """per-phase GPU ms of the last render with timing=True: {phase: (ms, launches)}"""
@@ -564,6 +582,35 @@ def render_mattes(scn, resolution: int = 720, samples: int = 1, *, keys: Sequenc
     dropped = ds.matte_dropped()
     out["dropped"] = {k: dropped[k] for k in keys}
     return out
+
+
+def render_ao(scn, resolution: int = 720, samples: int = 1, *, rays: int = 16, distance: float = float("inf"),
+              bias: float = 0.01, width: int = 0, window=None, camera: int = 0, device: int = 0,
+              return_stats: bool = False):
+    """Ambient occlusion on raytrace's sample grid: (H, W, 4) float32 {a, a, a, w}. Every camera
+    sample that hits a triangle casts `rays` (1..64) cosine-weighted rays over [bias, distance]
+    about its face-forward shading normal (the directions of ao_tables()); a hit on a line or a
+    point counts as unoccluded. a is the unoccluded share of the pixel's rays times the coverage
+    w (render_aovs' .w), so a / w is the ambient occlusion in [0, 1]. A count, so the same bits on
+    every run. `scn` is a Scene or a DeviceScene, as for raytrace."""
+    ds = _device_scene(scn, device)
+    p = render_params(resolution=resolution, samples=samples, width=width, camera=camera, window=window)
+    h, w = _window_shape(ds, p, window)
+    img = np.zeros((h, w, 4), np.float32)
+    ds.render_ao_into(p, img.ctypes.data, rays, distance, bias, device_memory=False)
+    if return_stats:
+        return img, ds.last_stats()
+    return img
+
+
+def ao_tables() -> tuple:
+    """the tables render_ao's kernel reads: dirs (64, 3) float32, the cosine-weighted directions
+    about +z of which a call uses the first `rays`, and rots (16, 2) float32, (cos, sin) of the
+    rotation about the normal that a camera sample applies to them"""
+    dirs, rots = np.zeros((64, 3), np.float32), np.zeros((16, 2), np.float32)
+    fp = C.POINTER(C.c_float)
+    check(N.lib.yrt_ao_tables(dirs.ctypes.data_as(fp), rots.ctypes.data_as(fp)), "yrt_ao_tables")
+    return dirs, rots
 
 
 def matte(m: dict, ids) -> np.ndarray:

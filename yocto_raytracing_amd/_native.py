@@ -132,6 +132,14 @@ class AdaptiveParams(C.Structure):
     _fields_ = [("base_samples", C.c_int), ("threshold", C.c_float), ("chunk_pixels", C.c_int)]
 
 
+# yrt_render_ao: occlusion rays per camera sample that hits a triangle (0: 16), their tmax and tmin
+YRT_AO_RAYS_MAX = 64
+
+
+class AoParams(C.Structure):
+    _fields_ = [("rays", C.c_int), ("distance", C.c_float), ("bias", C.c_float)]
+
+
 _vp = C.c_void_p
 _ip =C.POINTER(C.c_int)
 _sig = {
@@ -191,6 +199,10 @@ _sig = {
     "yrt_host_scene_instances": (C.c_int, [_vp, _ip, _ip, C.c_int, _ip]),
     "yrt_render_adaptive": (C.c_int, [_vp, C.POINTER(RenderParams), C.POINTER(AdaptiveParams), _vp, _vp, C.c_int, _vp]),
     "yrt_scene_adaptive_refined": (C.c_int, [_vp, C.POINTER(C.c_ulonglong)]),
+    "yrt_ao_params_default": (None, [C.POINTER(AoParams)]),
+    "yrt_ao_tables": (C.c_int, [C.POINTER(C.c_float), C.POINTER(C.c_float)]),
+    "yrt_render_ao": (C.c_int, [_vp, C.POINTER(RenderParams), C.POINTER(AoParams), _vp, C.c_int, _vp]),
+    "yrt_host_scene_shape_kinds": (C.c_int, [_vp, _ip, C.c_int, _ip]),
 }
 EXPORTS = tuple(_sig)
 

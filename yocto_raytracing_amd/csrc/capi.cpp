@@ -3,6 +3,7 @@
 // to a status code, with the message kept per thread (yrt_last_error).
 #include <hip/hip_runtime_api.h>
 
+#include <cfloat>
 #include <cmath>
 #include <cstdint>
 #include <cstring>
@@ -13,6 +14,8 @@
 #include <vector>
 
 #include "../../include/yrt.h"
+#include "ao_args.h"
+#include "ao_tables.h"
 #include "matte_args.h"
 #include "plane_staging.h"
 #include "yrt_render.h"
@@ -341,6 +344,21 @@ int yrt_host_scene_instances(const yrt_host_scene* hs, int* shape, int* material
         if (material) material[k] = s.instances[k].mat;
     }
     *n = (int)s.instances.size();
+    return YRT_OK;
+}
+
+int yrt_host_scene_shape_kinds(const yrt_host_scene* hs, int* kind, int cap, int* n) {
+    if (!hs || !n || (kind && cap < 0)) return YRT_ERR_INVALID_ARG;
+    // (the kinds of device_scene_create: the first primitive list of a shape that is not empty)
+    const auto& s = hs->scn;
+    for (size_t k = 0; kind && k < s.shapes.size() && (int)k < cap; k++) {
+        const auto& sh = s.shapes[k];
+        kind[k] = !sh.triangles.empty() ? yrt::kind_triangles
+                  : !sh.lines.empty()   ? yrt::kind_lines
+                  : !sh.points.empty()  ? yrt::kind_points
+                                        : yrt::kind_empty;
+    }
+    *n = (int)s.shapes.size();
     return YRT_OK;
 }
 
@@ -950,6 +968,58 @@ int yrt_render_adaptive(yrt_scene* s, const yrt_render_params* p, const yrt_adap
             hip_check(launch(nullptr), "adaptive render launch");
         else
             stage_host_planes(list, a.out_stride > r.tw, st, "hipMalloc(adaptive staging)", "adaptive render", launch);
+        return YRT_OK;
+    });
+}
+
+void yrt_ao_params_default(yrt_ao_params* a) {
+    if (!a) return;
+    a->rays = yrt::ao_rays_default;
+    a->distance = FLT_MAX;
+    a->bias = 0.01f;
+}
+
+static_assert(YRT_AO_RAYS_MAX == yrt::ao_dir_count, "a ray per direction of the table");
+
+int yrt_ao_tables(float dirs[64 * 3], float rots[16 * 2]) {
+    if (!dirs || !rots) return YRT_ERR_INVALID_ARG;
+    static const float d[yrt::ao_dir_count * 3] = {YRT_AO_DIRS};
+    static const float r[yrt::ao_rot_count * 2] = {YRT_AO_ROTS};
+    memcpy(dirs, d, sizeof d);
+    memcpy(rots, r, sizeof r);
+    return YRT_OK;
+}
+
+int yrt_render_ao(yrt_scene* s, const yrt_render_params* p, const yrt_ao_params* ap, float* out, int mem,
+                  void* stream) {
+    // (before any device call, and before the handle is looked at)
+    const char* bad = !s                 ? "yrt_render_ao: null scene handle"
+                      : !p               ? "yrt_render_ao: null params"
+                      : p->camera < 0    ? "yrt_render_ao: camera index out of range"
+                                         : yrt::ao_args_error(ap, out, mem);
+    if (bad) {
+        g_last_error = bad;
+        return YRT_ERR_INVALID_ARG;
+    }
+    return guarded([&] {
+        const yrt::ao_resolved ao = yrt::ao_resolve(*ap);
+        auto r = resolve(*s->ds, *p);
+        const yrt::dev_render_args a = frame_args(s, *p, &r, false);  // (its refusal comes before any device call)
+        hipStream_t st = (hipStream_t)stream;
+        hip_check(hipSetDevice(s->ds->device), "hipSetDevice");
+        // the counters are zeroed whatever the window: an empty one (a band offset without
+        // bands) launches nothing, and yrt_last_stats must not then report the call before
+        zero_counters(s, st);
+        s->last_stream = st;
+        if (r.tw <= 0 || r.th <= 0) return YRT_OK;
+        const yrt::plane_list list = yrt::ao_plane_list(out, (size_t)a.out_stride * r.th * 16);
+        auto launch = [&](void* staging) {
+            return yrt::launch_ao(*s->ds, a, ao.rays, ao.bias, ao.distance, list.plane(0, staging), s->counters, st);
+        };
+        if (mem == YRT_MEM_DEVICE)
+            hip_check(launch(nullptr), "ao kernel launch");
+        else
+            stage_host_planes(list, a.out_stride > r.tw, st, "hipMalloc(ao staging)", "ao render", launch);
         return YRT_OK;
     });
 }

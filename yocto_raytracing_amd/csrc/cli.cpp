@@ -11,7 +11,8 @@
 // (one plane per group of lights and the ambient plane, from the same render, as .npy files),
 // --mattes LIST with --matte-ranks 4|8 (ID mattes: per key the ranked ids covering each pixel and
 // their coverages, from one pass, as .npy files), --adaptive THRESHOLD with --base-samples N (the
-// image with adaptive supersampling, and the refined pixels' mask as a .npy file).
+// image with adaptive supersampling, and the refined pixels' mask as a .npy file),
+// --ao K[,DISTANCE[,BIAS]] (the ambient occlusion plane as a .npy file).
 #include <algorithm>
 #include <chrono>
 #include <cstdio>
@@ -57,7 +58,10 @@ namespace {
             "                       only where a pixel differs from a neighbour by more than F in a channel;\n"
             "                       prints the refined pixels and also writes OUT.refined.npy, (H, W) uint8\n"
             "                       (one GPU, a wavefront algorithm)\n"
-            "  --base-samples N     samples per axis of --adaptive's base frame [1]\n");
+            "  --base-samples N     samples per axis of --adaptive's base frame [1]\n"
+            "  --ao K[,DIST[,BIAS]] also write OUT.ao.npy, (H, W, 4) float32 {a, a, a, coverage}: a the share of K\n"
+            "                       (1 to 64) cosine-weighted rays per camera sample, from BIAS [0.01] to DIST\n"
+            "                       [unbounded], that nothing occludes, times the coverage (one GPU)\n");
     exit(msg ? 1 : 0);
 }
 
@@ -87,6 +91,26 @@ unsigned parse_names(const std::string& list, const char* const* names, int coun
         at = end + 1;
     }
     return mask;
+}
+
+// --ao's K[,distance[,bias]] over the defaults of yrt_ao_params_default
+yrt_ao_params parse_ao(const std::string& list) {
+    yrt_ao_params ao;
+    yrt_ao_params_default(&ao);
+    int field = 0;
+    for (size_t at = 0; at <= list.size(); field++) {
+        size_t end = list.find(',', at);
+        if (end == std::string::npos) end = list.size();
+        const std::string item = list.substr(at, end - at);
+        char* stop = nullptr;
+        if (field == 0) ao.rays = (int)strtol(item.c_str(), &stop, 10);
+        else if (field == 1) ao.distance = strtof(item.c_str(), &stop);
+        else if (field == 2) ao.bias = strtof(item.c_str(), &stop);
+        if (field > 2 || item.empty() || *stop) usage("--ao takes K[,DISTANCE[,BIAS]]");
+        at = end + 1;
+    }
+    if (ao.rays < 1 || ao.rays > YRT_AO_RAYS_MAX) usage("--ao: K must be from 1 to 64");
+    return ao;
 }
 
 // --light-groups' comma-separated group of each light
@@ -134,7 +158,8 @@ int main(int argc, char** argv) {
     unsigned aovs = 0, passes = 0, mattes = 0;
     int matte_ranks = 4;
     std::vector<int> light_groups;
-    bool groups = false, adaptive = false;
+    bool groups = false, adaptive = false, ao = false;
+    yrt_ao_params ao_params = {};
     float threshold = 0.0f;
     int base_samples = 1;
     std::string out = "out.png", scenein;
@@ -171,6 +196,7 @@ int main(int argc, char** argv) {
             if (!*v || *end || threshold != threshold) usage("bad value for --adaptive");
             adaptive = true;
         } else if (a == "--base-samples") base_samples = parse_int(val(), "--base-samples");
+        else if (a == "--ao") ao_params = parse_ao(val()), ao = true;
         else if (a == "-h" || a == "--help") usage(nullptr);
         else if (!a.empty() && a[0] == '-') usage(("unknown option " + a).c_str());
         else if (scenein.empty()) scenein = a;
@@ -181,6 +207,7 @@ int main(int argc, char** argv) {
     if (aovs && gpus > 1) usage("--aov renders on one GPU (--gpus 1)");
     if (mattes && gpus > 1) usage("--mattes renders on one GPU (--gpus 1)");
     if (matte_ranks != 4 && matte_ranks != 8) usage("--matte-ranks must be 4 or 8");
+    if (ao && gpus > 1) usage("--ao renders on one GPU (--gpus 1)");
     if (passes && gpus > 1) usage("--passes renders on one GPU (--gpus 1)");
     if (passes && algorithm == YRT_ALGO_MEGAKERNEL) usage("--passes needs a wavefront algorithm, not --algorithm megakernel");
     if (groups && gpus > 1) usage("--light-groups renders on one GPU (--gpus 1)");
@@ -337,6 +364,14 @@ int main(int argc, char** argv) {
                     fprintf(stderr, "matte %s: %llu samples dropped (more than %d ids in a pixel)\n", matte_names[k],
                             dropped[k], matte_ranks);
             }
+        }
+        if (ao) {
+            yrt_render_params p = scn->params;
+            p.resolution = resolution;
+            p.samples = samples;
+            std::vector<float> plane((size_t)hdr.width * hdr.height * 4);
+            yrt_cpp::check(yrt_render_ao(scn->on_device(), &p, &ao_params, plane.data(), YRT_MEM_HOST, nullptr), "render_ao");
+            save_npy(stem + ".ao.npy", plane.data(), hdr.width, hdr.height, "<f4");
         }
     } catch (const yrt_cpp::error& e) {
         fprintf(stderr, "%s\n", e.what());

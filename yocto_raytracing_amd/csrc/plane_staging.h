@@ -1,5 +1,5 @@
 // plane_staging.h -- the caller's planes of one call of yrt_render_aovs, yrt_render_mattes,
-// yrt_render_passes, yrt_render_light_groups or yrt_render_adaptive as one list, and where each lies in the device
+// yrt_render_passes, yrt_render_light_groups, yrt_render_adaptive or yrt_render_ao as one list, and where each lies in the device
 // staging of a call with host planes (capi.cpp stage_host_planes). Plain C++ without the HIP
 // runtime, so that it also builds into a stand-alone program under the host sanitizers
 // (tools/check_plane_staging.cpp).
@@ -88,6 +88,13 @@ inline plane_list adaptive_plane_list(float* out, unsigned char* refined, size_t
     plane_list l(pixels * 16);
     l.add(out, 0);
     if (refined) l.add_sized(refined, 1, pixels);
+    return l;
+}
+
+// yrt_render_ao: the one plane, slot 0
+inline plane_list ao_plane_list(float* out, size_t plane_bytes) {
+    plane_list l(plane_bytes);
+    l.add(out, 0);
     return l;
 }
 

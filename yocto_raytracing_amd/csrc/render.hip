@@ -385,3 +385,5 @@ hipError_t launch_tonemap(const float* rgba, int n, unsigned char* out, const to
 #include "mattes.hip"
 // adaptive supersampling (k_adaptive_*, launch_render_adaptive)
 #include "adaptive.hip"
+// ambient occlusion (k_ao, launch_ao), on the AOV pass's tile geometry
+#include "ao.hip"

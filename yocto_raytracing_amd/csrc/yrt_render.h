@@ -162,6 +162,13 @@ hipError_t launch_mattes(const device_scene& ds, const dev_render_args& args, un
                          const dev_matte_planes& out, unsigned long long* dropped, unsigned long long* counters,
                          hipStream_t stream);
 
+// the ambient occlusion pass (ao.hip k_ao): yrt_render_ao's plane, float4 per pixel in
+// launch_render's layout. rays (1..64), bias and distance are the resolved parameters
+// (ao_args.h): K, and the tmin and tmax of every occlusion ray. The caller zeroes the counter
+// lines before the launch; an empty window launches nothing.
+hipError_t launch_ao(const device_scene& ds, const dev_render_args& args, int rays, float bias, float distance,
+                     void* out_rgba, unsigned long long* counters, hipStream_t stream);
+
 // mirror levels the megakernel records per lane (render.hip); the wavefront pipeline
 // keeps per-level records in HBM and takes any max_depth
 constexpr int megakernel_max_depth = 16;
