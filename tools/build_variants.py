@@ -39,16 +39,19 @@ MAX_WORKERS = 16
 # the variants the suite runs (name -> defines): the compiled descent loops instead of the
 # generated assembly, the closest hit's stack with lane masks, the any-hit grid's items as
 # (block, light) pairs, frames of a few tiles split into several chunks, and level 0's shadow
-# rays and shading as two kernels where the default build fuses them, the persistent any-hit
-# grids' walk as the flat loop (packet_occluded_wide2) instead of the nested one, and the
-# camera rays' list-mode closest hit as the flat loop (packet_first) instead of the nested one
+# rays and shading as two kernels where the default build fuses them, the nested walks'
+# triangle leaves as compiled loops instead of the generated leaf scans (leaf_asm.h), the
+# persistent any-hit grids' walk as the flat loop (packet_occluded_wide2) instead of the nested
+# one, and the camera rays' list-mode closest hit as the flat loop (packet_first) instead of the
+# nested one
 TEST_VARIANTS = {
     "compiled": ["-DYRT_DESCENT_ASM=0", "-DYRT_WIDE_ASM=0"],
     "masks": ["-DYRT_STACK_MASKS=1"],
     "itemlights": ["-DYRT_SHADOW_ITEM_LIGHTS=0", "-DYRT_SHADOW_ITEM_RUN=8"],
     "chunks": ["-DYRT_CHUNK_LOG2=11", "-DYRT_MIRROR_CHUNK_LOG2=11"],
     "unfused": ["-DYRT_SHADOW_SHADE_FUSE=0"],
-    "flatany": ["-DYRT_ANY_NESTED=0"],
+    "cleaf": ["-DYRT_LEAF_ASM=0"],
+    "flatany":["-DYRT_ANY_NESTED=0"],
     "flatwalk": ["-DYRT_FIRST_NESTED=0"],
 }
 

@@ -42,6 +42,7 @@
 
 #include "descent_asm.h"
 #include "fast_div.h"
+#include "leaf_asm.h"
 #include "wide_asm.h"
 #include "trace_common.h"
 
@@ -1071,6 +1072,14 @@ __device__ __forceinline__ bool packet_first(const dev_scene_view& S, const ray3
 #if !defined(YRT_FIRST_NESTED)  // (its non-default build is the `flatwalk` library of tools/build_variants.py)
 #define YRT_FIRST_NESTED 1
 #endif
+// ---- the nested walks' triangle leaves as generated assembly (YRT_LEAF_ASM, default 3) ----
+// bit 0: packet_first_list's triangle loop is leaf_asm.h's leaf_scan_first; bit 1:
+// packet_occluded_nested's is leaf_scan_any (tools/gen_leaf_asm.py says what the blocks compute).
+// 0: both loops compiled (tools/build_variants.py "cleaf"). The flat walks, the line and point
+// leaves and render.hip's kernels are not concerned.
+#if !defined(YRT_LEAF_ASM)  // (its build with 0 is the `cleaf` library of tools/build_variants.py)
+#define YRT_LEAF_ASM 3
+#endif
 #define YRT_OCT_DISPATCH(oct, X) \
     switch (oct) {               \
         case 0: X(0); break;     \
@@ -1254,21 +1263,58 @@ __device__ __forceinline__ bool packet_first_list(const dev_scene_view& S, const
                             wc.box++, wc.prim += (unsigned)pcount;  // (stats build: shape leaves, primitive tests)
 #endif
                             if (kind == kind_triangles) {
-                                for (int i = pstart; i < pstart + pcount; i++) {
-                                    float4 pv[3];
-                                    ld_records_at<3>(S.sprims, (unsigned)(3 * i), pv);
-                                    float t, w1, w2;
-                                    const unsigned long long hm = tri_hit_mask<true>(
-                                        co, cd, tmin, tmax, xyz(pv[0]), xyz(pv[1]), xyz(pv[2]), t, w1, w2, lmask);
-                                    // most triangles hit no lane: their record-keeping selects are skipped
-                                    if (hm) {
-                                        const bool h = lane_in(hm);
-                                        tmax = h ? t : tmax;
-                                        hslot = h ? k : hslot;
-                                        hei = h ? ibits(pv[0].w) : hei;
-                                        hw1 = h ? w1 : hw1;
-                                        hw2 = h ? w2 : hw2;
-                                        leaf_hits |= hm;
+                                if constexpr ((YRT_LEAF_ASM & 1) != 0) {
+                                    // the scan comes back at a hit (the selects are compiled) and at a
+                                    // triangle whose den some lane cannot take rcp_nr of (the whole
+                                    // triangle is compiled), and is entered again behind either
+                                    const f4* pbase = sgpr_ptr(S.sprims);
+                                    uint32_t off = (uint32_t)uniform(pstart * 48);
+                                    const uint32_t end = (uint32_t)uniform((pstart + pcount) * 48);
+                                    while (off < end) {
+                                        float t, w1, w2;
+                                        unsigned long long hm;
+                                        leaf_scan_first(pbase, off, end, lmask, co, cd, tmin, tmax, hm, t, w1, w2);
+                                        if (!hm) {
+                                            if (off >= end) break;
+                                            float4 pv[3];
+                                            ld_records_at<3>(S.sprims, off / 16u, pv);
+                                            hm = tri_hit_mask<true>(co, cd, tmin, tmax, xyz(pv[0]), xyz(pv[1]),
+                                                                    xyz(pv[2]), t, w1, w2, lmask);
+                                        }
+                                        if (hm) {
+                                            int ei;  // the element word of the triangle that was hit
+                                            asm volatile("s_load_dword %0, %1, %2 offset:0xc\n s_waitcnt lgkmcnt(0)"
+                                                         : "=s"(ei)
+                                                         : "s"(pbase), "s"(off));
+                                            const bool h = lane_in(hm);
+                                            tmax = h ? t : tmax;
+                                            hslot = h ? k : hslot;
+                                            hei = h ? ei : hei;
+                                            hw1 = h ? w1 : hw1;
+                                            hw2 = h ? w2 : hw2;
+                                        }
+                                        off += 48u;
+                                    }
+                                    // (a lane of the leaf had no NaN tmax before it -- such a lane has left
+                                    // `alive` -- so one that has it now is one that hit here)
+                                    leaf_hits = lmask;
+                                } else {
+                                    for (int i = pstart; i < pstart + pcount; i++) {
+                                        float4 pv[3];
+                                        ld_records_at<3>(S.sprims, (unsigned)(3 * i), pv);
+                                        float t, w1, w2;
+                                        const unsigned long long hm = tri_hit_mask<true>(
+                                            co, cd, tmin, tmax, xyz(pv[0]), xyz(pv[1]), xyz(pv[2]), t, w1, w2, lmask);
+                                        // most triangles hit no lane: their record-keeping selects are skipped
+                                        if (hm) {
+                                            const bool h = lane_in(hm);
+                                            tmax = h ? t : tmax;
+                                            hslot = h ? k : hslot;
+                                            hei = h ? ibits(pv[0].w) : hei;
+                                            hw1 = h ? w1 : hw1;
+                                            hw2 = h ? w2 : hw2;
+                                            leaf_hits |= hm;
+                                        }
                                     }
                                 }
                             } else {
@@ -1921,25 +1967,65 @@ __device__ __forceinline__ bool packet_occluded_nested(const dev_scene_view& S, 
                         WSTAT(4, 1u);
                         WSTAT(5, (unsigned)count);
                         if (kind == kind_triangles) {
-                            // the table's address, once per leaf (held across the descent it
-                            // costs the kernel two more SGPR spills)
-                            const f4* abase = sgpr_ptr(reinterpret_cast<const f4*>(S.aprims));
-                            asm volatile("" : "+s"(abase));
-                            for (int i = first; i < first + count; i++) {
-                                float t, w1, w2;
-                                // v0, e1, e2 as 9 packed dwords (yrt_device.h aprims): 9 SGPRs, not 12
-                                sgpr8 a;
-                                int b;
-                                asm volatile("s_load_dwordx8 %0, %2, %3\n s_load_dword %1, %2, %3 offset:0x20\n"
-                                             " s_waitcnt lgkmcnt(0)"
-                                             : "=&s"(a), "=&s"(b)
-                                             : "s"(abase), "s"(uniform(i * 36)));
-                                const vec3f tv0 = {__int_as_float(a[0]), __int_as_float(a[1]), __int_as_float(a[2])};
-                                const vec3f te1 = {__int_as_float(a[3]), __int_as_float(a[4]), __int_as_float(a[5])};
-                                const vec3f te2 = {__int_as_float(a[6]), __int_as_float(a[7]), __int_as_float(b)};
-                                // (per lane, not tri_hit_mask: packet_occluded_wide2)
-                                const bool h = tri_hit_nb<true>(co, cd, tmin, tmax, tv0, te1, te2, t, w1, w2, inl, mask);
-                                leaf_hit |= (h && inl) ? 1 : 0;
+                            if constexpr ((YRT_LEAF_ASM & 2) != 0) {
+                                // the scan ORs the lanes that hit into `gone` itself (no per-lane
+                                // leaf_hit); it comes back early at a triangle whose den some lane
+                                // cannot take rcp_nr of -- that one is compiled -- and is entered again
+                                // behind it
+                                const f4* abase = sgpr_ptr(reinterpret_cast<const f4*>(S.aprims));
+                                asm volatile("" : "+s"(abase));
+                                uint32_t off = (uint32_t)uniform(first * 36);
+                                const uint32_t end = (uint32_t)uniform((first + count) * 36);
+                                unsigned long long lm = mask;  // the leaf's lanes not answered yet
+                                while (off < end) {
+                                    leaf_scan_any(abase, off, end, lm, gone, co, cd, tmin, tmax);
+                                    if (off >= end) break;
+                                    float t, w1, w2;
+                                    sgpr8 a;
+                                    int b;
+                                    asm volatile("s_load_dwordx8 %0, %2, %3\n s_load_dword %1, %2, %3 offset:0x20\n"
+                                                 " s_waitcnt lgkmcnt(0)"
+                                                 : "=&s"(a), "=&s"(b)
+                                                 : "s"(abase), "s"(off));
+                                    const vec3f tv0 = {__int_as_float(a[0]), __int_as_float(a[1]),
+                                                       __int_as_float(a[2])};
+                                    const vec3f te1 = {__int_as_float(a[3]), __int_as_float(a[4]),
+                                                       __int_as_float(a[5])};
+                                    const vec3f te2 = {__int_as_float(a[6]), __int_as_float(a[7]), __int_as_float(b)};
+                                    // (the leaf's lanes still unanswered: a lane that is answered stays so)
+                                    const bool in = lane_in(lm);
+                                    const bool h =
+                                        tri_hit_nb<true>(co, cd, tmin, tmax, tv0, te1, te2, t, w1, w2, in, lm);
+                                    const unsigned long long hm = ballot(h && in);
+                                    gone |= hm;
+                                    lm &= ~hm;
+                                    off += 36u;
+                                    if (!lm) break;
+                                }
+                            } else {
+                                // the table's address, once per leaf (held across the descent it
+                                // costs the kernel two more SGPR spills)
+                                const f4* abase = sgpr_ptr(reinterpret_cast<const f4*>(S.aprims));
+                                asm volatile("" : "+s"(abase));
+                                for (int i = first; i < first + count; i++) {
+                                    float t, w1, w2;
+                                    // v0, e1, e2 as 9 packed dwords (yrt_device.h aprims): 9 SGPRs, not 12
+                                    sgpr8 a;
+                                    int b;
+                                    asm volatile("s_load_dwordx8 %0, %2, %3\n s_load_dword %1, %2, %3 offset:0x20\n"
+                                                 " s_waitcnt lgkmcnt(0)"
+                                                 : "=&s"(a), "=&s"(b)
+                                                 : "s"(abase), "s"(uniform(i * 36)));
+                                    const vec3f tv0 = {__int_as_float(a[0]), __int_as_float(a[1]),
+                                                       __int_as_float(a[2])};
+                                    const vec3f te1 = {__int_as_float(a[3]), __int_as_float(a[4]),
+                                                       __int_as_float(a[5])};
+                                    const vec3f te2 = {__int_as_float(a[6]), __int_as_float(a[7]), __int_as_float(b)};
+                                    // (per lane, not tri_hit_mask: packet_occluded_wide2)
+                                    const bool h =
+                                        tri_hit_nb<true>(co, cd, tmin, tmax, tv0, te1, te2, t, w1, w2, inl, mask);
+                                    leaf_hit |= (h && inl) ? 1 : 0;
+                                }
                             }
                         } else {
                             for (int i = first; i < first + count; i++) {
