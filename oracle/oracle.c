@@ -413,7 +413,22 @@ static v3 eval_tex(const texture* t, v2 uv) {
     return add(add(add(cij, ci1j), cij1), ci1j1);
 }
 
-typedef struct { long long rays; int max_depth; long long truncated; } ctx;
+typedef struct { long long rays; int max_depth; long long truncated; int pow_mode; } ctx;
+
+/* the specular pow (raytrace.cpp:146-160), the one libm call whose result the device may
+ * round differently. mode 0: powf, the reference. -1 / +1: powf's result moved one float
+ * toward 0 / toward +inf, except where every correct pow is exact (y == 0, x == 1) or the
+ * result is not a finite positive number; the two renders bracket every pow that returns
+ * one of the two floats around the true value. 2: the host model of the device's f64
+ * path, (float)exp2(y*log2(x)) rounded once. 3: exp2f(y*log2f(x)), an inexact f32 power
+ * that the parity tests must reject. */
+static float spec_powf(float x, float y, int mode) {
+    if (mode == 2) return y == 0.0f ? 1.0f : (float)exp2((double)y * log2((double)x));
+    if (mode == 3) return y == 0.0f ? 1.0f : exp2f(y * log2f(x));
+    float p = powf(x, y);
+    if (mode == 0 || !isfinite(p) || !(p > 0.0f) || y == 0.0f || x == 1.0f) return p;
+    return nextafterf(p, mode < 0 ? 0.0f : INFINITY);
+}
 
 static v3 shade(const scene* s, v3 amb, const ray* r, int depth, ctx* cx) {
     float dist = 0;
@@ -484,10 +499,10 @@ static v3 shade(const scene* s, v3 amb, const ray* r, int depth, ctx* cx) {
             if (pnh < 0.0f) pnh *= -1;
             float sinnl = sqrtf(1.0f - pnl), sinnh = sqrtf(1.0f - pnh);
             ld = muls(ld, sinnl);
-            ls = muls(ls, powf(sinnh, ns));
+            ls = muls(ls, spec_powf(sinnh, ns, cx->pow_mode));
         } else {
             ld = muls(ld, fmaxsel(0.0f, dot(n, l)));
-            ls = muls(ls, powf(fmaxsel(0.0f, dot(n, h)), ns));
+            ls = muls(ls, spec_powf(fmaxsel(0.0f, dot(n, h)), ns, cx->pow_mode));
         }
         c = add(c, add(ld, ls));
     }
@@ -651,12 +666,13 @@ int oracle_set_threads(int n) {
 /* raytrace() (raytrace.cpp:213-254) for image rows rows[0..nrows) and columns
  * [x0, x0+ncols); width 0 -> round(aspect*res). out: nrows*ncols*4 floats.
  * max_depth 0 = unbounded recursion (the reference). Returns rays traced
- * (negative on error); *truncated gets the number of depth-capped paths. */
-long long oracle_render_rows(void* vs, float amb, int cami, int resolution, int width, int samples,
-                             int max_depth, const int* rows, int nrows, int x0, int ncols, float* out,
-                             long long* truncated) {
+ * (negative on error, an unknown pow_mode included); *truncated gets the number of
+ * depth-capped paths. pow_mode: spec_powf's; 0 is the reference. */
+long long oracle_render_rows_pow(void* vs, float amb, int cami, int resolution, int width, int samples,
+                                 int max_depth, const int* rows, int nrows, int x0, int ncols, float* out,
+                                 long long* truncated, int pow_mode) {
     scene* s = (scene*)vs;
-    if (cami < 0 || cami >= s->ncam || samples <= 0) return -1;
+    if (cami < 0 || cami >= s->ncam || samples <= 0 || pow_mode < -1 || pow_mode > 3) return -1;
     const camera* cam = &s->cams[cami];
     int W = width > 0 ? width : (int)roundf(cam->aspect * resolution), H = resolution;
     v3 a = {amb, amb, amb};
@@ -664,7 +680,7 @@ long long oracle_render_rows(void* vs, float amb, int cami, int resolution, int 
 #pragma omp parallel for schedule(dynamic, 1) reduction(+ : rays, trunc)
     for (int r = 0; r < nrows; r++) {
         int j = rows[r];
-        ctx cx = {0, max_depth, 0};
+        ctx cx = {0, max_depth, 0, pow_mode};
         for (int c = 0; c < ncols; c++) {
             int i = x0 + c;
             v4 acc = {0, 0, 0, 0};
@@ -691,6 +707,27 @@ long long oracle_render_rows(void* vs, float amb, int cami, int resolution, int 
     }
     if (truncated) *truncated = trunc;
     return rays;
+}
+
+long long oracle_render_rows(void* vs, float amb, int cami, int resolution, int width, int samples,
+                             int max_depth, const int* rows, int nrows, int x0, int ncols, float* out,
+                             long long* truncated) {
+    return oracle_render_rows_pow(vs, amb, cami, resolution, width, samples, max_depth, rows, nrows, x0,
+                                  ncols, out, truncated, 0);
+}
+
+/* 1 when a pixel is a monotone function of every specular pow: the pow result is only
+ * multiplied by Ks, Ke/r^2 and, along a reflected path, Kr, so no component of those may
+ * be negative (or NaN) in any material. Else 0, and mode -1 / +1 renders bound nothing. */
+int oracle_pow_monotone(void* vs) {
+    const scene* s = (const scene*)vs;
+    for (int i = 0; i < s->nmat; i++) {
+        const material* m = &s->mats[i];
+        const float k[9] = {m->ks.x, m->ks.y, m->ks.z, m->ke.x, m->ke.y, m->ke.z, m->kr.x, m->kr.y, m->kr.z};
+        for (int j = 0; j < 9; j++)
+            if (!(k[j] >= 0.0f)) return 0;
+    }
+    return 1;
 }
 
 /* camera ray of pixel (i,j) sub-sample (ii,jj): o.xyz d.xyz tmin tmax */

@@ -53,9 +53,9 @@ def digests() -> dict:
 @lru_cache(maxsize=None)
 def oracle_lib():
     so = ROOT / "oracle" / "liboracle.so"
-    if not so.exists():
-        subprocess.run(["make", "-C", str(ROOT / "oracle"), "liboracle.so"], check=True,
-                       capture_output=True)
+    # unconditionally: a liboracle.so older than oracle.c lacks the entries below; a no-op
+    # when the library is fresh
+    subprocess.run(["make", "-C", str(ROOT / "oracle"), "liboracle.so"], check=True, capture_output=True)
     lib = C.CDLL(str(so))
     lib.oracle_load.restype = C.c_void_p
     lib.oracle_load.argtypes = [C.c_char_p]
@@ -65,6 +65,9 @@ def oracle_lib():
     lib.oracle_render_rows.restype = C.c_longlong
     lib.oracle_render_rows.argtypes = [C.c_void_p, C.c_float, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                        C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+    lib.oracle_render_rows_pow.restype = C.c_longlong
+    lib.oracle_render_rows_pow.argtypes = lib.oracle_render_rows.argtypes + [C.c_int]
+    lib.oracle_pow_monotone.argtypes = [C.c_void_p]
     lib.oracle_trace.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 5
     lib.oracle_camera_ray.argtypes = [C.c_void_p] + [C.c_int] * 8 + [C.c_void_p]
     return lib
@@ -92,7 +95,10 @@ class Oracle:
         return w.value, h.value
 
     def render(self, resolution, samples, amb=0.1, rows=None, x0=0, ncols=None, width=0, max_depth=0,
-               camera=0):
+               camera=0, pow_mode=0):
+        """pow_mode: the specular pow (oracle.c spec_powf). 0 powf, the reference; -1 / +1
+        powf moved one float down / up; 2 the host model of the device's f64 path; 3 an
+        inexact f32 power that the parity bar must reject."""
         W, H = self.image_size(resolution, camera)
         if width:
             W = width
@@ -100,12 +106,36 @@ class Oracle:
         ncols = W - x0 if ncols is None else ncols
         out = np.zeros((len(rows), ncols, 4), np.float32)
         trunc = C.c_longlong(0)
-        n = self.lib.oracle_render_rows(self.h, amb, camera, resolution, width, samples, max_depth,
-                                        rows.ctypes.data, len(rows), x0, ncols, out.ctypes.data,
-                                        C.byref(trunc))
+        n = self.lib.oracle_render_rows_pow(self.h, amb, camera, resolution, width, samples, max_depth,
+                                            rows.ctypes.data, len(rows), x0, ncols, out.ctypes.data,
+                                            C.byref(trunc), pow_mode)
         if n < 0:
             raise RuntimeError("oracle render failed")
         return out, int(n), int(trunc.value)
+
+    def envelope(self, *args, **kwargs):
+        """render()'s arguments -> (ref, lo, hi, nrays, trunc): the reference frame and the
+        channel-wise bounds of every frame whose specular pow returns one of the two floats
+        around the true value. lo/hi are the renders with every such pow one
+        float below / above powf's: between the pow and the pixel there are only multiplies
+        by non-negative factors, adds and one division by a positive constant, all monotone
+        under round-to-nearest, and neither visibility nor the reflected paths depend on
+        colour. Refuses a scene in which a negative Ks, Ke or Kr breaks that argument."""
+        assert "pow_mode" not in kwargs
+        if not self.lib.oracle_pow_monotone(self.h):
+            raise ValueError("a material has a negative (or NaN) Ks, Ke or Kr component: the pixel is not a "
+                             "monotone function of the specular pow, the +-1 float renders bound nothing")
+        ref, nrays, trunc = self.render(*args, **kwargs)
+        down, nd, td = self.render(*args, pow_mode=-1, **kwargs)
+        up, nu, tu = self.render(*args, pow_mode=+1, **kwargs)
+        assert (nd, td) == (nrays, trunc) and (nu, tu) == (nrays, trunc), "the paths depend on the pow"
+        lo, hi = np.minimum(down, up), np.maximum(down, up)
+        ok = ~np.isnan(ref)
+        assert np.array_equal(np.isnan(lo), ~ok) and np.array_equal(np.isnan(hi), ~ok)
+        assert ((lo[ok] <= ref[ok]) & (ref[ok] <= hi[ok])).all(), "the reference lies outside its own envelope"
+        for a in (ref, lo, hi):
+            a.setflags(write=False)
+        return ref, lo, hi, nrays, trunc
 
     def trace(self, rays, any_hit=False):
         rays = np.ascontiguousarray(rays, np.float32)
@@ -218,3 +248,84 @@ def assert_same_floats(got, want):
     gn, wn = np.isnan(got), np.isnan(want)
     np.testing.assert_array_equal(gn, wn)
     np.testing.assert_array_equal(got[~gn].view(np.uint32), want[~wn].view(np.uint32))
+
+
+@lru_cache(maxsize=None)
+def oracle_envelope(name_or_path, *args, **kwargs):
+    """Oracle(name_or_path).envelope(*args, **kwargs), computed once per test session (the
+    arrays are read-only). Arguments must be hashable: pass rows as a tuple."""
+    if "rows" in kwargs and kwargs["rows"] is not None:
+        kwargs = dict(kwargs, rows=np.asarray(kwargs["rows"], np.int32))
+    return Oracle(name_or_path).envelope(*args, **kwargs)
+
+
+def _offenders(mask, got, ref, lo, hi, limit=5):
+    idx = np.argwhere(mask)
+    rows = []
+    for i in idx[:limit]:
+        i = tuple(i)
+        rows.append(f"  {i}: got {got[i].view(np.uint32):#010x} ref {ref[i].view(np.uint32):#010x} "
+                    f"lo {lo[i].view(np.uint32):#010x} hi {hi[i].view(np.uint32):#010x}")
+    return f"{len(idx)} channels, the first {len(rows)} (index: bits of got/ref/lo/hi):\n" + "\n".join(rows)
+
+
+def assert_frame_parity(got, ref, lo, hi, what, rows=None):
+    """The parity bar of a frame against the oracle: assert_frame_in_envelope
+    and the count cap. ref, lo, hi come from Oracle.envelope at the frame's scene and
+    parameters.
+      * same shape, float32, NaN exactly where ref has NaN (as assert_same_floats);
+      * where lo and hi have the same bits, got has those bits (signs of zeros count);
+      * elsewhere lo <= got <= hi;
+      * at most max(2, size // 10000) non-NaN channels differ from ref's bits: a cap, so
+        that a pow that is merely within an ulp cannot hide inside the envelope;
+      * close_mask(got, ref), the earlier absolute bar.
+    rows (for frames whose oracle render takes many seconds): lo and hi cover only
+    got[rows]; the envelope checks run there, the others on the whole frame.
+    Prints one line per call (what, differing, sensitive, channels) for the -s log."""
+    differ, lo, hi = assert_frame_in_envelope(got, ref, lo, hi, what, rows)
+    cap = max(2, ref.size // 10000)
+    assert int(differ.sum()) <= cap, (f"{what}: more than {cap} channels off the reference's bits: "
+                                      + _offenders(differ, np.asarray(got), ref, lo, hi))
+
+
+def assert_frame_in_envelope(got, ref, lo, hi, what, rows=None):
+    """assert_frame_parity without the count cap, for the one kind of frame whose reference
+    alone exceeds it: where nearly every channel is a sum of specular terms only (the
+    SPECULAR pass), glibc powf and a correctly rounded pow already differ in more than
+    max(2, channels / 10000) channels (tests/test_gpu_passes.py). Returns the mask of the
+    channels that differ from ref's bits, and lo and hi at the frame's size."""
+    got = np.asarray(got)
+    assert got.dtype == np.float32 and ref.dtype == np.float32, f"{what}: {got.dtype} vs {ref.dtype}"
+    assert got.shape == ref.shape, f"{what}: shape {got.shape} vs {ref.shape}"
+    covered = np.ones(got.shape, bool)
+    if rows is not None:
+        rows = np.asarray(rows)
+        covered[:] = False
+        covered[rows] = True
+        full_lo, full_hi = ref.copy(), ref.copy()
+        assert lo.shape == hi.shape == full_lo[rows].shape, f"{what}: envelope shape {lo.shape}"
+        full_lo[rows], full_hi[rows] = lo, hi
+        lo, hi = full_lo, full_hi
+        assert np.array_equal(np.isnan(lo), np.isnan(ref)), f"{what}: the envelope is not this frame's"
+        with np.errstate(invalid="ignore"):
+            assert not ((lo > ref) | (ref > hi)).any(), f"{what}: the envelope is not this frame's"
+    assert lo.shape == hi.shape == got.shape, f"{what}: envelope shape {lo.shape}"
+    gb, rb, lb, hb = (a.view(np.uint32) for a in (got, ref, lo, hi))
+    nan = np.isnan(ref)
+    ok = ~nan
+    pinned = ok & covered & (lb == hb)
+    sensitive = ok & covered & (lb != hb)
+    differ = ok & (gb != rb)
+    print(f"parity {what}: differing {int(differ.sum())} sensitive {int(sensitive.sum())} channels {got.size}"
+          + ("" if rows is None else f" (envelope on {len(rows)} of {got.shape[0]} rows)"))
+    bad = np.isnan(got) != nan
+    assert not bad.any(), f"{what}: NaN channels differ from the reference's: " + _offenders(bad, got, ref, lo, hi)
+    bad = pinned & (gb != lb)
+    assert not bad.any(), (f"{what}: off the reference's bits where no pow within one float can move them: "
+                           + _offenders(bad, got, ref, lo, hi))
+    with np.errstate(invalid="ignore"):
+        bad = sensitive & ~((lo <= got) & (got <= hi))
+    assert not bad.any(), f"{what}: outside the +-1 float pow envelope: " + _offenders(bad, got, ref, lo, hi)
+    bad = ok & ~close_mask(got, ref)
+    assert not bad.any(), f"{what}: beyond ATOL/RTOL: " + _offenders(bad, got, ref, lo, hi)
+    return differ, lo, hi

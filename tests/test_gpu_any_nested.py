@@ -28,7 +28,7 @@ points, and the closest hit of each one's ray towards the added light -- one occ
 which intersect_any's walk has to meet unless it finds another first. Those occluders include
 instances of each kind of frame and both the line and the point shape.
 
-Two of the cases are also compared with the oracle's render (helpers.close_mask), under both
+Two of the cases are also compared with the oracle's render (helpers.assert_frame_parity), under both
 libraries.
 
 A child that fails -- a signal, an abort, its time limit, an error -- fails its test, and no later
@@ -47,7 +47,7 @@ from functools import lru_cache
 import numpy as np
 import pytest
 
-from helpers import ROOT, Oracle, close_mask
+from helpers import ROOT, Oracle, assert_frame_parity
 
 CHILD_TIMEOUT = 300  # seconds: a child loads torch, uploads its scenes and renders tiny frames
 STATS = ("rays", "camera_samples", "shadow_rays", "shadow_rays_culled", "depth_truncated")
@@ -162,7 +162,8 @@ def test_nested_any_hit_renders_the_flat_walk_s_bits(cid, tmp_path_factory):
 
 @lru_cache(maxsize=None)
 def _oracle_render(scene, width, height, samples, max_depth):
-    return Oracle(scene).render(height, samples, width=width, max_depth=max_depth)
+    """(ref, lo, hi, rays, truncated): the oracle's frame and its pow envelope"""
+    return Oracle(scene).envelope(height, samples, width=width, max_depth=max_depth)
 
 
 @pytest.mark.gpu
@@ -172,10 +173,10 @@ def test_both_walks_match_the_oracle(cid, lib, tmp_path_factory):
     c = CASES[cid]
     got = _child("cases", lib, tmp_path_factory)
     img, st = got["z"][f"{cid}.img"], got["meta"]["cases"][cid]["stats"]
-    ref, nrays, trunc = _oracle_render(c["scene"], c["width"], c["resolution"], c["samples"], c["max_depth"])
+    ref, lo, hi, nrays, trunc = _oracle_render(c["scene"], c["width"], c["resolution"], c["samples"], c["max_depth"])
     assert img.shape == ref.shape
     assert st["rays"] == nrays and st["depth_truncated"] == trunc
-    assert close_mask(img, ref).all(), f"max|diff| {np.abs(img.astype(np.float64) - ref).max()}"
+    assert_frame_parity(img, ref, lo, hi, f"any nested {cid} {lib}")
 
 
 @pytest.mark.gpu

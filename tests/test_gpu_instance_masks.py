@@ -25,7 +25,7 @@ from __future__ import annotations
 import numpy as np
 import pytest
 
-from helpers import Oracle, close_mask
+from helpers import Oracle, assert_frame_parity
 
 pytestmark = pytest.mark.gpu
 
@@ -126,9 +126,6 @@ def test_instance_masks_on_off_equal_oracle(yrt, tmp_path, camera):
         assert l_on["camera_instances_masked"] > 0 and l_on["camera_entries"] < 32 * l_on["camera_lists"], l_on
     np.testing.assert_array_equal(on.view(np.uint32), off.view(np.uint32))
     assert st_on == st_off and st_on["shadow_rays"] > 0
-    ref, n, trunc = Oracle(str(path)).render(res, spp)
+    ref, lo, hi, n, trunc = Oracle(str(path)).envelope(res, spp)
     assert trunc == 0 and n == st_on["rays"]
-    differ = int(np.sum(on.view(np.uint32) != ref.view(np.uint32)))
-    print(f"camera={camera}: {differ} of {on.size} channels not bit-exact vs oracle")
-    assert close_mask(on, ref).all()
-    assert np.mean(on.view(np.uint32) == ref.view(np.uint32)) > 0.99
+    assert_frame_parity(on, ref, lo, hi, f"instance masks camera={camera}")

@@ -12,7 +12,7 @@ from __future__ import annotations
 import numpy as np
 import pytest
 
-from helpers import Oracle, close_mask, scene_path
+from helpers import assert_frame_parity, oracle_envelope, scene_path
 
 pytestmark = pytest.mark.gpu
 
@@ -63,12 +63,9 @@ def test_staged_walks_same_image_as_oracle(yrt, name, res, spp, any_hit):
     assert not l_on["camera"] and not l_on["bundles"], l_on
     np.testing.assert_array_equal(on.view(np.uint32), off.view(np.uint32))
     assert st_on == st_off
-    ref, n, trunc = Oracle(name).render(res, spp)
+    ref, lo, hi, n, trunc = oracle_envelope(name, res, spp)
     assert trunc == 0 and n == st_on["rays"]
-    differ = int(np.sum(on.view(np.uint32) != ref.view(np.uint32)))
-    print(f"{name} {res}p {spp}x{spp} staged: {differ} of {on.size} channels not bit-exact vs oracle")
-    assert close_mask(on, ref).all()
-    assert np.mean(on.view(np.uint32) == ref.view(np.uint32)) > 0.99
+    assert_frame_parity(on, ref, lo, hi, f"{name} {res}p {spp}x{spp} staged")
 
 
 def test_staging_turns_the_lists_off_and_back(yrt):

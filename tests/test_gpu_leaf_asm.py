@@ -25,7 +25,7 @@ of the two degenerate triangles for the rays that hit the four-triangle leaf's i
 float32 and in tri_hit_mask's order.
 
 Two of the cases and the leaf scene are also compared with the oracle's render
-(helpers.close_mask), under both libraries.
+(helpers.assert_frame_parity), under both libraries.
 
 A child that fails -- a signal, an abort, its time limit, an error -- fails its test, and no later
 test starts another.
@@ -43,7 +43,7 @@ from functools import lru_cache
 import numpy as np
 import pytest
 
-from helpers import ROOT, Oracle, close_mask
+from helpers import ROOT, Oracle, assert_frame_parity
 
 sys.path.insert(0, str(ROOT / "tests"))
 import leaf_asm_worker as W  # noqa: E402
@@ -194,7 +194,7 @@ def test_the_leaf_scene_has_zero_and_denormal_determinants(leaf_scene):
         assert both.sum() >= 8, (name, int(both.sum()))
     assert (first["hit"] & (first["inst"] == inst["single"])).sum() >= 4
     for ns in W.SAMPLES:
-        img, nrays, _ = _oracle_render(str(path), WIDTH, HEIGHT, ns, 16, view)
+        img, _, _, nrays, _ = _oracle_render(str(path), WIDTH, HEIGHT, ns, 16, view)
         assert np.isfinite(img).all() and nrays > WIDTH * HEIGHT * ns * ns
 
 
@@ -233,7 +233,8 @@ def test_leaf_scans_render_the_compiled_loops_bits(cid, tmp_path_factory):
 
 @lru_cache(maxsize=None)
 def _oracle_render(scene, width, height, samples, max_depth, camera=0):
-    return Oracle(scene).render(height, samples, width=width, max_depth=max_depth, camera=camera)
+    """(ref, lo, hi, rays, truncated): the oracle's frame and its pow envelope"""
+    return Oracle(scene).envelope(height, samples, width=width, max_depth=max_depth, camera=camera)
 
 
 @pytest.mark.gpu
@@ -243,10 +244,10 @@ def test_both_leaf_forms_match_the_oracle(cid, lib, tmp_path_factory):
     c = CASES[cid]
     got = _child("cases", lib, tmp_path_factory)
     img, st = got["z"][f"{cid}.img"], got["meta"]["cases"][cid]["stats"]
-    ref, nrays, trunc = _oracle_render(c["scene"], c["width"], c["resolution"], c["samples"], c["max_depth"])
+    ref, lo, hi, nrays, trunc = _oracle_render(c["scene"], c["width"], c["resolution"], c["samples"], c["max_depth"])
     assert img.shape == ref.shape
     assert st["rays"] == nrays and st["depth_truncated"] == trunc
-    assert close_mask(img, ref).all(), f"max|diff| {np.abs(img.astype(np.float64) - ref).max()}"
+    assert_frame_parity(img, ref, lo, hi, f"leaf asm {cid} {lib}")
 
 
 @pytest.mark.gpu
@@ -267,7 +268,7 @@ def test_the_leaf_scene_matches_the_oracle(ns, lib, tmp_path_factory):
     got = _child("leaf", lib, tmp_path_factory)
     meta = got["meta"]
     img, st = got["z"][f"s{ns}.img"], meta["frames"][f"s{ns}"]["stats"]
-    ref, nrays, trunc = _oracle_render(str(got["dir"] / "leaf.yrtscene"), WIDTH, HEIGHT, ns, 16, meta["camera"])
+    ref, lo, hi, nrays, trunc = _oracle_render(str(got["dir"] / "leaf.yrtscene"), WIDTH, HEIGHT, ns, 16, meta["camera"])
     assert img.shape == ref.shape
     assert st["rays"] == nrays and st["depth_truncated"] == trunc
-    assert close_mask(img, ref).all(), f"max|diff| {np.abs(img.astype(np.float64) - ref).max()}"
+    assert_frame_parity(img, ref, lo, hi, f"leaf scene s{ns} {lib}")

@@ -5,7 +5,7 @@ levels. The five-light scene (light_groups_scene.py) takes the kernels that read
 bytes per light, passes_scene's two lights the ones that load them with the surface.
 
 A group's plane is the beauty of the scene variant that keeps the group's lights, rendered with
-ambient 0: within helpers.ATOL / RTOL of the oracle's (the device pow) and bit-equal to the
+ambient 0: helpers.assert_frame_parity against the oracle's (the device pow) and bit-equal to the
 GPU's own render of the uploaded variant. The ambient plane is the variant without lights,
 rendered with the ambient: bit-equal to both (no pow). The beauty is yrt.raytrace's, with its
 counters. Then the depth cut, the recomposition on the file fixtures, and the plumbing.
@@ -18,7 +18,7 @@ import pytest
 
 import light_groups_scene as LS
 import passes_scene as PS
-from helpers import ATOL, MIRROR_DEPTH, ROOT, RTOL, Oracle, assert_same_floats, close_mask, scene_path
+from helpers import MIRROR_DEPTH, ROOT, Oracle, assert_frame_parity, assert_same_floats, scene_path
 
 pytestmark = pytest.mark.gpu
 
@@ -68,12 +68,14 @@ def file_scene(yrt, name):
 
 
 def oracle_variant(yrt, tmp_path_factory, more, mirrors, lit, s, amb):
+    """the oracle's beauty of a variant and its pow envelope (helpers.Oracle.envelope):
+    (ref, lo, hi)"""
     key = (more, mirrors, tuple(lit), s, amb)
     if key not in _oracle:
-        img, _, _ = Oracle(built(yrt, tmp_path_factory, more, mirrors, lit)[1]).render(RES, s, amb=amb, width=WIDTH,
-                                                                                      max_depth=16)
+        img, lo, hi, _, _ = Oracle(built(yrt, tmp_path_factory, more, mirrors, lit)[1]).envelope(
+            RES, s, amb=amb, width=WIDTH, max_depth=16)
         assert img.shape == (RES, WIDTH, 4) and np.isfinite(img).all()
-        _oracle[key] = img
+        _oracle[key] = (img, lo, hi)
     return _oracle[key]
 
 
@@ -102,11 +104,8 @@ def test_each_plane_is_the_beauty_of_its_variant(yrt, tmp_path_factory, setup, m
     lit_pixels = []
     for g, plane in enumerate(out["groups"]):
         lit = LS.lights_of(group_of, g)
-        want = oracle_variant(yrt, tmp_path_factory, more, mirrors, lit, s, 0.0)
-        differ = int((plane.view(np.uint32) != want.view(np.uint32)).sum())
-        print(f"{setup} mirrors={mirrors} s={s} group {g}: {differ} of {plane.size} channels differ in bits from "
-              f"the oracle, max|diff| {np.abs(plane.astype(np.float64) - want).max():.3g}")
-        assert close_mask(plane, want, ATOL, RTOL).all(), g
+        want, lo, hi = oracle_variant(yrt, tmp_path_factory, more, mirrors, lit, s, 0.0)
+        assert_frame_parity(plane, want, lo, hi, f"light groups {setup} mirrors={mirrors} s={s} group {g}")
         gpu = yrt.raytrace(built(yrt, tmp_path_factory, more, mirrors, lit)[2], (0.0, 0.0, 0.0), RES, s, width=WIDTH)
         same_bits(plane, gpu)
         lit_pixels.append(int((plane[..., :3] > 0).any(axis=-1).sum()))
@@ -114,7 +113,7 @@ def test_each_plane_is_the_beauty_of_its_variant(yrt, tmp_path_factory, setup, m
     for a in range(len(out["groups"])):  # and no two planes are one image
         for b in range(a):
             assert (out["groups"][a] != out["groups"][b]).any(axis=-1).sum() >= 100, (a, b)
-    want = oracle_variant(yrt, tmp_path_factory, more, mirrors, (), s, PS.AMB)
+    want = oracle_variant(yrt, tmp_path_factory, more, mirrors, (), s, PS.AMB)[0]
     assert_same_floats(out["ambient"], want)
     same_bits(out["ambient"], yrt.raytrace(built(yrt, tmp_path_factory, more, mirrors, ())[2], PS.AMB, RES, s, width=WIDTH))
     assert (out["ambient"][..., :3] > 0).any()

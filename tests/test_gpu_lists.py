@@ -11,7 +11,7 @@ from __future__ import annotations
 import numpy as np
 import pytest
 
-from helpers import Oracle, close_mask, scene_path
+from helpers import Oracle, assert_frame_parity, oracle_envelope, scene_path
 
 pytestmark = pytest.mark.gpu
 
@@ -42,13 +42,6 @@ def render(yrt, ds, mode, res, spp, window=None):
     return img, st, ds.tile_lists()
 
 
-def check_oracle(img, ref, what):
-    differ = int(np.sum(img.view(np.uint32) != ref.view(np.uint32)))
-    print(f"{what}: {differ} of {img.size} channels not bit-exact vs oracle")
-    assert close_mask(img, ref).all()
-    assert np.mean(img.view(np.uint32) == ref.view(np.uint32)) > 0.99
-
-
 @pytest.mark.parametrize("name,res,spp", [
     ("instance10000", 90, 8),    # 160x90: the bottom tile row is cut by the frame
     ("instance10000", 37, 3),    # 66x37, 9 spp: 64-sample items straddle pixels
@@ -65,9 +58,9 @@ def test_lists_on_off_same_image_as_oracle(yrt, name, res, spp):
     assert l_on["camera_lists"] > 0 and l_on["bundle_lists"] > 0
     np.testing.assert_array_equal(on.view(np.uint32), off.view(np.uint32))
     assert st_on == st_off
-    ref, n, trunc = Oracle(name).render(res, spp)
+    ref, lo, hi, n, trunc = oracle_envelope(name, res, spp)
     assert trunc == 0 and n == st_on["rays"]
-    check_oracle(on, ref, f"{name} {res}p {spp}x{spp} lists on")
+    assert_frame_parity(on, ref, lo, hi, f"{name} {res}p {spp}x{spp} lists on")
 
 
 def test_lists_on_in_a_window(yrt):
@@ -81,8 +74,8 @@ def test_lists_on_in_a_window(yrt):
     assert l_on["camera"] and l_on["bundles"]
     np.testing.assert_array_equal(on.view(np.uint32), off.view(np.uint32))
     x0, y0, w, h = win
-    ref, _, _ = Oracle(name).render(res, spp, rows=np.arange(y0, y0 + h), x0=x0, ncols=w)
-    check_oracle(on, ref, "instance10000 window lists on")
+    ref, lo, hi, _, _ = Oracle(name).envelope(res, spp, rows=np.arange(y0, y0 + h), x0=x0, ncols=w)
+    assert_frame_parity(on, ref, lo, hi, "instance10000 window lists on")
 
 
 def test_lists_auto(yrt):
@@ -161,9 +154,9 @@ def test_lists_synthetic_lights(yrt, tmp_path, nlights, rotated, bundles):
     assert l_on["camera"] and l_on["bundles"] == bundles, l_on
     np.testing.assert_array_equal(on.view(np.uint32), off.view(np.uint32))
     assert st_on == st_off and st_on["shadow_rays"] > 0
-    ref, n, _ = Oracle(str(path)).render(res, spp)
+    ref, lo, hi, n, _ = Oracle(str(path)).envelope(res, spp)
     assert n == st_on["rays"]
-    check_oracle(on, ref, f"grid {nlights} lights rotated={rotated}")
+    assert_frame_parity(on, ref, lo, hi, f"grid {nlights} lights rotated={rotated}")
 
 
 def test_tile_lists_argument_errors(yrt):
@@ -190,9 +183,8 @@ def test_lists_follow_the_view(yrt):
     or off -- equals the oracle's render from that camera"""
     name, res, spp = "instance10000", 180, 4
     ds = host(yrt, name).upload(0)
-    orc = Oracle(name)
     for cam in (0, 1, 2, 3, 4, 0):
-        ref, n, _ = orc.render(res, spp, camera=cam)
+        ref, lo, hi, n, _ = oracle_envelope(name, res, spp, camera=cam)
         imgs = []
         for mode in ("auto", "on", "off"):
             ds.set_tile_lists(mode)
@@ -201,5 +193,5 @@ def test_lists_follow_the_view(yrt):
             imgs.append(img)
         for img in imgs[1:]:
             np.testing.assert_array_equal(img.view(np.uint32), imgs[0].view(np.uint32))
-        check_oracle(imgs[0], ref, f"instance10000 camera {cam}")
+        assert_frame_parity(imgs[0], ref, lo, hi, f"instance10000 camera {cam}")
 

@@ -26,7 +26,7 @@ from __future__ import annotations
 import numpy as np
 import pytest
 
-from helpers import Oracle, close_mask
+from helpers import Oracle, assert_frame_parity
 
 pytestmark = pytest.mark.gpu
 
@@ -110,14 +110,11 @@ def test_shadow_cull_equals_oracle(yrt, tmp_path, near_light):
         np.testing.assert_array_equal(walked.view(np.uint32), on.view(np.uint32))
         assert st_w["shadow_rays_culled"] == 0 and st_w["rays"] == st_on["rays"]
         assert st_w["shadow_rays"] == st_on["shadow_rays"]
-    ref, n, trunc = Oracle(str(path)).render(res, spp)
+    ref, lo, hi, n, trunc = Oracle(str(path)).envelope(res, spp)
     assert trunc == 0 and n == st_on["rays"]  # culled rays are counted: the reference's count
     walked_rays = st_on["rays"] - st_on["shadow_rays_culled"]
     assert walked_rays + st_on["shadow_rays_culled"] == n and walked_rays < n
-    differ = int(np.sum(on.view(np.uint32) != ref.view(np.uint32)))
-    print(f"near_light={near_light}: {differ} of {on.size} channels not bit-exact vs oracle")
-    assert close_mask(on, ref).all()
-    assert np.mean(on.view(np.uint32) == ref.view(np.uint32)) > 0.99
+    assert_frame_parity(on, ref, lo, hi, f"shadow cull near_light={near_light}")
 
 
 def test_shadow_cull_counts_at_c4_scale(yrt):
