@@ -38,6 +38,7 @@
 #include "item_magic.h"
 #include "packet_trace.h"
 #include "trace_common.h"
+#include "wf_workspace.h"
 #include "yrt_render.h"
 
 namespace yrt {
@@ -81,12 +82,6 @@ constexpr int CHUNK_LOG2 = YRT_CHUNK_LOG2;
 constexpr int MIRROR_CHUNK_LOG2 = YRT_MIRROR_CHUNK_LOG2;
 static_assert(CHUNK_LOG2 >= 0 && CHUNK_LOG2 <= 29 && MIRROR_CHUNK_LOG2 >= 0 && MIRROR_CHUNK_LOG2 <= 29,
               "a chunk's samples are counted in an int");
-constexpr int TILE = 8;         // pixel tiles of TILE x TILE in the sample enumeration
-
-// the render's list sums (k_list_stats, yrt_scene_tile_lists / yrt_scene_tile_list_masks):
-// camera-list entries, camera lists, bundle-list entries, bundle lists, then the instances the
-// camera lists' and the bundle lists' masks exclude
-constexpr int list_sums = 6;
 
 struct wf_buffers {
     f4* surf0;          // {p.xyz, info}: info = mat*4+kind, -1 miss, -2 not a sample
@@ -133,18 +128,7 @@ struct wf_buffers {
     unsigned long long* lstats;  // the render's list sums (k_list_stats, list_sums of them)
 };
 
-// Mirror levels are compacted into level_segments segments of B.seg slots: segment g of
-// level k + 1 holds the mirror rays spawned by k_shade's blocks b with b % 8 == g, at
-// [g * seg, g * seg + count), each segment behind its own counter on its own 128-byte
-// line. (One counter for the whole level serialised k_shade's block atomics: about 7 ns
-// each on one address, ~1 ms of c3's level-0 shading.) Consumers walk the segments in
-// turn, so their waves stay full except for each segment's last one.
-#ifndef YRT_LEVEL_SEGMENTS
-#define YRT_LEVEL_SEGMENTS 8
-#endif
-constexpr int level_segments = YRT_LEVEL_SEGMENTS;  // divides the 2048-block grid of the mirror levels
-static_assert(2048 % level_segments == 0, "segment bound (run()) assumes level_segments | 2048");
-constexpr int count_stride = 32;  // ints: one 128-byte line per counter
+// the counter of segment g of a mirror level (level_segments, count_stride: wf_workspace.h)
 __device__ __forceinline__ int* seg_counter(int* count, int level, int g) {
     return count + (level * level_segments + g) * count_stride;
 }
@@ -487,11 +471,7 @@ __device__ __forceinline__ ray3 camera_ray_w(const dev_camera& cam, int W, int H
 // any-hit answer does not depend on which inner boxes were tested.
 // A bundle whose light is rotated, whose hit points are not finite or whose list would be
 // longer walks the tree.
-#ifndef YRT_BUNDLE_ITEMS
-#define YRT_BUNDLE_ITEMS 64  // 64-sample items per bundle (at most 64: one per lane of the list builder)
-#endif
-constexpr int bundle_g = YRT_BUNDLE_ITEMS;
-static_assert(bundle_g >= 1 && bundle_g <= 64, "one item per lane of k_bundle_lists");
+// (bundle_g items per bundle, bundle_recs, bundle_max_lights, camera_list_max: wf_workspace.h)
 #ifndef YRT_BUNDLE_MIN_TOP
 #define YRT_BUNDLE_MIN_TOP 8  // bundles only when the instance level's wide tree has this many records
 #endif
@@ -506,13 +486,6 @@ static_assert(bundle_g >= 1 && bundle_g <= 64, "one item per lane of k_bundle_li
 // (the list builders also mark the instances of a listed leaf that their cone / hull excludes,
 // and the walks skip them: k_camera_lists, k_bundle_lists; dev_scene_view ibox)
 constexpr int bundle_max = 16;        // candidate leaves per list
-constexpr int bundle_recs = 5;        // wide records per list: a chain (3 + 3 + 3 + 3 + 4 leaves)
-constexpr int bundle_max_lights = 8;  // more lights: no bundles (the lists' memory grows with them)
-// camera rays walk per-tile leaf lists (k_camera_lists, packet_first's list mode)
-#ifndef YRT_CAMERA_LIST_MAX
-#define YRT_CAMERA_LIST_MAX 32  // leaves per tile list (more: the tile's rays walk the tree)
-#endif
-constexpr int camera_list_max = YRT_CAMERA_LIST_MAX;
 
 // wave-wide min / max with DPP row rotations and row broadcasts (VALU only, no LDS round
 // trips): every row of 16 lanes folds itself, rows 1 and 3 take rows 0 and 2 (row_bcast:15),
@@ -1326,10 +1299,7 @@ static __device__ unsigned long long g_list_time[3][65536][4];
 // be measured on its own.)
 #define YRT_BUNDLE_FUSED 0
 #endif
-constexpr int super_bundles = 4;
-static_assert(bundle_g * super_bundles <= 4 * 64, "bundle_box: up to four items per lane");
-constexpr int super_max = 32;
-constexpr int super_list_f4 = 1 + 2 * super_max;  // {count} then {lo, word} {hi, 0} per leaf
+// (super_bundles, super_max, super_list_f4: wf_workspace.h)
 
 // one wave per (super-bundle, light): its list at B.slists
 __global__ __launch_bounds__(256) void k_bundle_super(dev_scene_view S, wf_buffers B, int n_items) {
@@ -2602,8 +2572,7 @@ __global__ __launch_bounds__(SB, FUSE ? shade_pass_waves : YRT_SHADE_LEVEL_WAVES
 // k_shade_groups has a body of its own, like the fused k_shade_passes: shade_hit keeps one c
 // per call. A change to shade_hit is to be made here too (tests/test_gpu_light_groups.py
 // compares every plane with yrt_render of its variant bit for bit).
-constexpr int group_planes = light_groups_max + 2;  // the groups, the ambient, the beauty
-struct group_buffers {
+struct group_buffers {  // (group_planes planes: wf_workspace.h)
     int nplanes;              // planes in use, [0, nplanes)
     unsigned amb_mask;        // bit k: plane k adds la (the ambient plane and the beauty)
     // behind the workspace: tab[k], tab[k + 1] bound plane k's entries of tab + group_planes + 1,
@@ -3029,87 +2998,48 @@ __global__ __launch_bounds__(WF_BLOCK) void k_accumulate_groups(dev_render_args 
     accumulate_plane(A, C, [&] { return G.smp[k]; }, [&] { return G.out[k]; });
 }
 
-size_t align_up(size_t x) { return (x + 255) & ~size_t(255); }
-
-// the per-level, per-segment mirror-ray counters (seg_counter)
-size_t count_bytes(int nlevels) { return sizeof(int) * ((size_t)nlevels + 1) * level_segments * count_stride; }
-
-// shadow bundles: items (64-sample blocks) and bundles of a chunk of cap samples
-size_t bundle_items(int cap) { return ((size_t)cap + 63) / 64; }
-size_t bundle_count(int cap) { return (bundle_items(cap) + bundle_g - 1) / bundle_g; }
-int bundle_lights(int nlights) { return nlights <= bundle_max_lights ? nlights : 0; }
-size_t super_count(int cap) { return (bundle_count(cap) + super_bundles - 1) / super_bundles; }
-
-// camera lists: 8x8-pixel tiles of a chunk of cap samples at spp samples per pixel
-size_t camera_tiles(int cap, int spp) { return ((size_t)cap / (size_t)spp + TILE * TILE - 1) / (TILE * TILE); }
-
-// pass_planes_n planes of pass_samples per-sample pass values (yrt_render_passes in the unfused
-// and mirror shapes) follow yrt_render's workspace, which is the same with or without them
-size_t workspace_bytes(int cap, int spp, int nlights, int nlevels, int pass_planes_n = 0, size_t pass_samples = 0) {
-    if (pass_planes_n > 0)
-        return workspace_bytes(cap, spp, nlights, nlevels) + (size_t)pass_planes_n * align_up(16 * pass_samples);
-    size_t c = (size_t)cap;
-    size_t b = align_up(count_bytes(nlevels)) + align_up(32 * sizeof(unsigned)) +
-               align_up(list_sums * sizeof(unsigned long long));
-    b += align_up(16 * c) * 2 + align_up(4 * c) + align_up(c * std::max(nlights, 1)) + align_up(16 * c);
-    const size_t gl = bundle_count(cap) * bundle_lights(nlights);
-    b += align_up(32 * bundle_items(cap)) + 2 * align_up(4 * gl) + align_up((size_t)bundle_recs * wide_record_bytes * gl);
-    b += align_up(super_count(cap) * bundle_lights(nlights) * super_list_f4 * 16);
-    const size_t nt = camera_tiles(cap, spp);
-    b += 2 * align_up(4 * nt) + align_up(nt * camera_list_max * 32);
-    // levels >= 1: ray_o, ray_d; levels < last: rec0, rec1 (one slab each)
-    if (nlevels > 1) b += 4 * align_up((size_t)(nlevels - 1) * 16 * c);
-    return b;
-}
-
-// the light groups' share, behind yrt_render's workspace (the same with or without them): the
-// table of lights sorted by plane; per-sample values of nplanes - 1 planes (plane 0's are B.rad)
-// in the unfused and mirror shapes (smp_samples of them, else 0); mirror-level records of
-// nplanes - 1 planes (plane 0's are B.rec0_)
-size_t group_table_ints(int nlights) { return group_planes + 1 + 2 * (size_t)nlights; }
-size_t group_bytes(int cap, int nlights, int nlevels, int nplanes, size_t smp_samples) {
-    size_t b = align_up(sizeof(int) * group_table_ints(nlights));
-    if (smp_samples) b += (size_t)(nplanes - 1) * align_up(16 * smp_samples);
-    if (nlevels > 1) b += (size_t)(nplanes - 1) * align_up((size_t)(nlevels - 1) * 16 * (size_t)cap);
-    return b;
-}
-
-wf_buffers carve(void* base, int cap, int spp, int nlights, int nlevels) {
+// The workspace at `base` as the kernels' buffers: every slab of the walk (wf_workspace.h) to the
+// member it is. P, G: the planes of yrt_render_passes or yrt_render_light_groups, else null.
+wf_buffers carve(void* base, const workspace_shape& s, pass_buffers* P, group_buffers* G) {
     wf_buffers B = {};
-    char* p = (char*)base;
-    size_t c = (size_t)cap;
-    auto take = [&](size_t bytes) {
-        char* q = p;
-        p += align_up(bytes);
-        return (void*)q;
-    };
-    B.count = (int*)take(count_bytes(nlevels));
-    B.queue = (unsigned*)take(32 * sizeof(unsigned));
-    B.lstats = (unsigned long long*)take(list_sums * sizeof(unsigned long long));
-    B.surf0 = (f4*)take(16 * c);
-    B.surf1 = (f4*)take(16 * c);
-    B.surfv = (float*)take(4 * c);
-    B.occl = (unsigned char*)take(c * std::max(nlights, 1));
-    B.rad = (f4*)take(16 * c);
-    const size_t gl = bundle_count(cap) * bundle_lights(nlights);
-    B.pbox = (f4*)take(32 * bundle_items(cap));
-    B.lcount = (int*)take(4 * gl);
-    B.lskip = (int*)take(4 * gl);
-    B.lists = (f4*)take((size_t)bundle_recs * wide_record_bytes * gl);
-    B.slists = (f4*)take(super_count(cap) * bundle_lights(nlights) * super_list_f4 * 16);
-    const size_t nt = camera_tiles(cap, spp);
-    B.ccount = (int*)take(4 * nt);
-    B.cskip = (int*)take(4 * nt);
-    B.clist = (f4*)take(nt * camera_list_max * 32);
-    if (nlevels > 1) {
-        const size_t slab = (size_t)(nlevels - 1) * 16 * c;
-        B.ray_o_ = (f4*)take(slab);
-        B.ray_d_ = (f4*)take(slab);
-        B.rec0_ = (f4*)take(slab);
-        B.rec1_ = (f4*)take(slab);
-    }
-    B.capacity = cap;
-    B.nlevels = nlevels;
+    workspace_carver w(base);
+    int pass = -1;  // the wanted pass that took the last slab_pass_smp
+    walk_workspace(s, [&](wf_slab slab, int k, size_t bytes) {
+        void* const p = w.take(bytes);
+        switch (slab) {
+            case slab_count: B.count = (int*)p; break;
+            case slab_queue: B.queue = (unsigned*)p; break;
+            case slab_lstats: B.lstats = (unsigned long long*)p; break;
+            case slab_surf0: B.surf0 = (f4*)p; break;
+            case slab_surf1: B.surf1 = (f4*)p; break;
+            case slab_surfv: B.surfv = (float*)p; break;
+            case slab_occl: B.occl = (unsigned char*)p; break;
+            case slab_rad: B.rad = (f4*)p; break;
+            case slab_pbox: B.pbox = (f4*)p; break;
+            case slab_lcount: B.lcount = (int*)p; break;
+            case slab_lskip: B.lskip = (int*)p; break;
+            case slab_lists: B.lists = (f4*)p; break;
+            case slab_slists: B.slists = (f4*)p; break;
+            case slab_ccount: B.ccount = (int*)p; break;
+            case slab_cskip: B.cskip = (int*)p; break;
+            case slab_clist: B.clist = (f4*)p; break;
+            case slab_ray_o: B.ray_o_ = (f4*)p; break;
+            case slab_ray_d: B.ray_d_ = (f4*)p; break;
+            case slab_rec0: B.rec0_ = (f4*)p; break;
+            case slab_rec1: B.rec1_ = (f4*)p; break;
+            case slab_pass_smp:
+                do pass++;
+                while (!(P->mask >> pass & 1));
+                P->smp[pass] = (f4*)p;
+                break;
+            case slab_group_tab: G->tab = (const int*)p; break;
+            case slab_group_smp: G->smp[k] = (f4*)p; break;
+            case slab_group_rec: G->rec[k] = (f4*)p; break;
+        }
+    });
+    if (G) G->smp[0] = B.rad, G->rec[0] = B.rec0_;
+    B.capacity = s.cap;
+    B.nlevels = s.nlevels;
     return B;
 }
 
@@ -3170,6 +3100,17 @@ hipError_t make_level_counts(device_scene& ds) {
     if (!ds.level_count_ev) return hipEventCreateWithFlags(&ds.level_count_ev, hipEventDisableTiming);
     return hipSuccess;
 }
+// the list sums of the last render that built lists, on the host (behind list_stats_ev)
+hipError_t make_list_stats(device_scene& ds) {
+    if (!ds.list_stats_host) {
+        hipError_t e =
+            hipHostMalloc((void**)&ds.list_stats_host, list_sums * sizeof(unsigned long long), hipHostMallocDefault);
+        if (e != hipSuccess) return e;
+        memset(ds.list_stats_host, 0, list_sums * sizeof(unsigned long long));
+    }
+    if (!ds.list_stats_ev) return hipEventCreateWithFlags(&ds.list_stats_ev, hipEventDisableTiming);
+    return hipSuccess;
+}
 hipError_t fetch_level_counts(device_scene& ds, const wf_buffers& B, int level, hipStream_t stream) {
     hipError_t e = hipMemcpyAsync(ds.level_count_host, B.count + (size_t)level * level_segments * count_stride,
                                   sizeof(int) * level_segments * count_stride, hipMemcpyDeviceToHost, stream);
@@ -3197,6 +3138,118 @@ void launch_chunk_setup(const device_scene& ds, const wf_buffers& B, int nrec, c
                        counter_words);
 }
 
+// How a call is split into chunks, and the carved workspace of one chunk. A unit is a pixel
+// (run(): whole tiles, so `granule` is TILE * TILE) or a ray (run_rays(): spp 1, granule 1).
+struct chunk_plan {
+    int nlevels;    // one level per trace_first call a sample may make
+    bool fuse;      // one level and whole pixels per block: the shading kernels sum the pixels themselves
+    int per_chunk;  // units of a chunk
+    int seg, cap;   // slots per segment of a mirror level, and per sample record
+    wf_buffers B;
+};
+// P, G: the call's copy of its passes' or groups' planes, which gets their slabs; else null
+hipError_t plan_chunks(device_scene& ds, const dev_render_args& A, long long units, int granule, int spp,
+                       pass_buffers* P, group_buffers* G, chunk_plan& plan) {
+    // one level per trace_first call a camera sample may make (A.max_depth; the reference
+    // recursion is unbounded, so the caller's depth is kept as given)
+    const int nlevels = plan.nlevels = ds.reflective ? std::max(A.max_depth, 1) : 1;
+    // (k_shade FUSE; one-wave fused blocks lose: +9 %)
+    const bool fuse = plan.fuse = nlevels == 1 && WF_BLOCK % spp == 0;
+    // the passes' per-sample planes (16 B per wanted pass and sample; the fused shape keeps
+    // them in LDS)
+    const int smp_planes = P && !fuse ? __builtin_popcount(P->mask & ((1u << pass_count) - 1)) : 0;
+    auto units_for = [&](long long tgt) {
+        const int u = (int)std::max<long long>(1, std::min<long long>(units, tgt / spp));
+        return (u + granule - 1) / granule * granule;
+    };
+    // slots per sample record: a chunk's samples, and with mirror levels a slack so that
+    // every segment of a level holds whatever k_shade's blocks of that segment spawn: at
+    // level 0 one round of 256-sample blocks puts at most cap / 8 + 256 rays into a
+    // segment, at later levels (a grid-stride grid of 2048 blocks over up to 8 input
+    // segments) at most cap / 8 + 8 * 256
+    auto seg_of = [&](int u) { return u * spp / level_segments + level_segments * WF_BLOCK; };
+    auto cap_of = [&](int u) { return nlevels > 1 ? level_segments * seg_of(u) : u * spp; };
+    auto shape_of = [&](int u) {
+        const size_t samples = (size_t)u * spp;
+        return workspace_shape{cap_of(u), spp, ds.nlights, nlevels, smp_planes, samples,
+                               G ? G->nplanes : 0, fuse ? 0 : samples};
+    };
+    plan.per_chunk =
+        units_for(chunk_target(ds, A, [&](long long tgt) { return workspace_bytes(shape_of(units_for(tgt))); }));
+    plan.seg = seg_of(plan.per_chunk);
+    plan.cap = cap_of(plan.per_chunk);
+    const workspace_shape shape = shape_of(plan.per_chunk);
+    if (hipError_t e = grow_workspace(ds, workspace_bytes(shape)); e != hipSuccess) return e;
+    plan.B = carve(ds.work, shape, P, G);
+    plan.B.seg = plan.seg;
+    plan.B.need_v = ds.view.ntextures > 0;
+    return nlevels > 1 ? make_level_counts(ds) : hipSuccess;
+}
+
+// f(std::bool_constant<b>()): a run-time bool as a template argument inside a generic lambda
+template <class F>
+decltype(auto) with_bool(bool b, F&& f) {
+    return b ? f(std::true_type()) : f(std::false_type());
+}
+
+// f(std::bool_constant<PACKET>(), SE()): the walk of a call. The packet walk's per-wave stack
+// holds 32-bit node indices (no narrow/wide split needed); the per-lane walks' stack entries SE
+// are 16-bit where every node index fits them.
+template <class F>
+hipError_t with_walk(const device_scene& ds, bool packet, F&& f) {
+    if (packet) return f(std::true_type(), uint32_t());
+    if (ds.narrow_stack) return f(std::false_type(), uint16_t());
+    return f(std::false_type(), uint32_t());
+}
+
+constexpr int stride_grid = 2048;  // grid-stride kernels: 8 blocks of 256 per CU
+
+// The levels of one chunk of nsamp samples whose level-0 closest hits are in B. A level with no
+// mirror rays ends the chunk's recursion. The level's k_bounce is queued before the host waits
+// for the level's ray count, so the GPU works on it while the count comes back; only a level
+// that turns out empty costs a launch (one k_bounce of no rays).
+// shadow0(): launches level 0's shadow rays where the caller has a kernel of its own for them;
+// false: they run on the k_shadow grid like every later level's.
+// shade(level, grid): launches the kernel that shades a level.
+// level0_shaded: shadow0's kernel has shaded level 0 too.
+template <bool COUNT, bool PACKET, typename SE, class SHADOW0, class SHADE>
+hipError_t run_levels(device_scene& ds, const wf_buffers& B, int nlevels, int nsamp, const float4& cam4,
+                      unsigned long long* counters, hipStream_t stream, SHADOW0&& shadow0, bool level0_shaded,
+                      SHADE&& shade) {
+    phase_timer& T = ds.timer;
+    constexpr int TB = shadow_block<PACKET>();
+    for (int level = 0; level < nlevels; level++) {
+        if (level > 0) {
+            int t = T.begin(phase_bounce, stream);
+            hipLaunchKernelGGL((k_bounce<COUNT, PACKET, SE>), dim3(stride_grid), dim3(WF_BLOCK), 0, stream, ds.view,
+                               level, B, counters);
+            T.end(t, stream);
+            bool any;
+            if (hipError_t e = level_has_rays(ds, any); e != hipSuccess) return e;
+            if (!any) break;
+        }
+        if (ds.nlights > 0) {
+            int t = T.begin(phase_shadow, stream);
+            if (level > 0 || !shadow0()) {
+                const dim3 sg(level ? stride_grid * WF_BLOCK / TB : (nsamp + TB - 1) / TB, ds.nlights);
+                with_bool(!COUNT && PACKET && ds.wide_ok, [&](auto wide) {
+                    hipLaunchKernelGGL((k_shadow<COUNT, PACKET, SE, decltype(wide)::value>), sg, dim3(TB), 0, stream,
+                                       ds.view, level, nsamp, B, counters, cam4);
+                });
+            }
+            T.end(t, stream);
+        }
+        if (level == 0 && level0_shaded) continue;
+        int t = T.begin(phase_shade, stream);
+        shade(level, dim3(level ? stride_grid : (nsamp + WF_BLOCK - 1) / WF_BLOCK));
+        T.end(t, stream);
+        if (level + 1 < nlevels) {
+            if (hipError_t e = fetch_level_counts(ds, B, level + 1, stream); e != hipSuccess) return e;
+        }
+    }
+    return hipSuccess;
+}
+
 // passes: yrt_render_passes' planes (P.mask, P.out; out is then P.out[pass_count], the beauty,
 // or null), shaded by k_shade_passes and summed by k_accumulate_passes; null: yrt_render
 // groups: yrt_render_light_groups' planes (nplanes, amb_mask, out; ds.group_tab their table),
@@ -3208,93 +3261,38 @@ hipError_t run(device_scene& ds, const dev_render_args& A, float4* out, unsigned
     const int tiles_x = (A.tile_w + TILE - 1) / TILE;
     const int tiles_y = (A.tile_h + TILE - 1) / TILE;
     const long long npix_total = (long long)tiles_x * tiles_y * TILE * TILE;
-    // one level per trace_first call a camera sample may make (A.max_depth; the reference
-    // recursion is unbounded, so the caller's depth is kept as given)
-    const int nlevels = ds.reflective ? std::max(A.max_depth, 1) : 1;
-    auto cap_for = [&](long long tgt) {
-        int pix = (int)std::max<long long>(1, std::min<long long>(npix_total, tgt / spp));
-        pix = ((pix + TILE * TILE - 1) / (TILE * TILE)) * TILE * TILE;
-        return pix;
-    };
-    // slots per sample record: a chunk's samples, and with mirror levels a slack so that
-    // every segment of a level holds whatever k_shade's blocks of that segment spawn: at
-    // level 0 one round of 256-sample blocks puts at most cap / 8 + 256 rays into a
-    // segment, at later levels (a grid-stride grid of 2048 blocks over up to 8 input
-    // segments) at most cap / 8 + 8 * 256
-    auto seg_of = [&](int pix) { return pix * spp / level_segments + level_segments * WF_BLOCK; };
-    auto cap_of = [&](int pix) { return nlevels > 1 ? level_segments * seg_of(pix) : pix * spp; };
-    // one level and whole pixels per block: shade sums the pixels itself (k_shade FUSE;
-    // one-wave fused blocks lose: +9 %)
-    const bool fuse = nlevels == 1 && WF_BLOCK % spp == 0;
-    // the passes' per-sample planes (16 B per wanted pass and sample; the fused shape keeps
-    // them in LDS)
-    const int smp_planes = passes && !fuse ? __builtin_popcount(passes->mask & ((1u << pass_count) - 1)) : 0;
-    auto bytes_of = [&](long long tgt) {
-        const int pix = cap_for(tgt);
-        return workspace_bytes(cap_of(pix), spp, ds.nlights, nlevels, smp_planes, (size_t)pix * spp) +
-               (groups ? group_bytes(cap_of(pix), ds.nlights, nlevels, groups->nplanes, fuse ? 0 : (size_t)pix * spp) : 0);
-    };
-    const int pix_per_chunk = cap_for(chunk_target(ds, A, bytes_of));
-    const int seg = seg_of(pix_per_chunk);
-    const int cap = cap_of(pix_per_chunk);
+    pass_buffers P = passes ? *passes : pass_buffers{};
+    group_buffers G = groups ? *groups : group_buffers{};
+    chunk_plan plan;
+    if (hipError_t e = plan_chunks(ds, A, npix_total, TILE * TILE, spp, passes ? &P : nullptr,
+                                   groups ? &G : nullptr, plan);
+        e != hipSuccess)
+        return e;
+    const int nlevels = plan.nlevels, pix_per_chunk = plan.per_chunk;
+    const bool fuse = plan.fuse;
+    wf_buffers& B = plan.B;
+    B.trel = ds.trel;
     // the frame's division pairs and range decisions, the same for every chunk (item_magic.h)
     const item_magic M = make_item_magic(spp, A.samples, tiles_x, A.band, (uint64_t)npix_total,
                                          (uint64_t)pix_per_chunk * spp, (uint64_t)tiles_y * TILE, A.width, A.height,
                                          A.x0, A.y0);
-    const size_t group_smp = fuse ? 0 : (size_t)pix_per_chunk * spp;
-    const size_t need = workspace_bytes(cap, spp, ds.nlights, nlevels, smp_planes, (size_t)pix_per_chunk * spp) +
-                        (groups ? group_bytes(cap, ds.nlights, nlevels, groups->nplanes, group_smp) : 0);
-    if (hipError_t e = grow_workspace(ds, need); e != hipSuccess) return e;
-    wf_buffers B = carve(ds.work, cap, spp, ds.nlights, nlevels);
-    B.trel = ds.trel;
-    B.seg = seg;
-    B.need_v = ds.view.ntextures > 0;
-    pass_buffers P = {};
-    if (passes) {
-        P = *passes;
-        char* at = (char*)ds.work + workspace_bytes(cap, spp, ds.nlights, nlevels);
-        for (int k = 0; k < pass_count && smp_planes; k++)
-            if (P.mask >> k & 1) P.smp[k] = (f4*)at, at += align_up(16 * (size_t)pix_per_chunk * spp);
-    }
-    group_buffers G = {};
     if (groups) {
-        G = *groups;
-        char* at = (char*)ds.work + workspace_bytes(cap, spp, ds.nlights, nlevels);
         // (the table's source, ds.group_tab, outlives the call; a copy from pageable memory is
         // staged before hipMemcpyAsync returns)
-        if (hipError_t e = hipMemcpyAsync(at, ds.group_tab.data(), sizeof(int) * ds.group_tab.size(),
+        if (hipError_t e = hipMemcpyAsync((void*)G.tab, ds.group_tab.data(), sizeof(int) * ds.group_tab.size(),
                                           hipMemcpyHostToDevice, stream);
             e != hipSuccess)
             return e;
-        G.tab = (const int*)at, at += align_up(sizeof(int) * group_table_ints(ds.nlights));
-        G.smp[0] = B.rad, G.rec[0] = B.rec0_;
-        for (int k = 1; k < G.nplanes && group_smp; k++) G.smp[k] = (f4*)at, at += align_up(16 * group_smp);
-        for (int k = 1; k < G.nplanes && nlevels > 1; k++)
-            G.rec[k] = (f4*)at, at += align_up((size_t)(nlevels - 1) * 16 * (size_t)cap);
     }
     bool list_stats = false;
     ds.last_camera_lists = ds.last_bundles = false;
-    if (!ds.list_stats_host) {
-        // the sums of the last render that built lists (behind list_stats_ev)
-        hipError_t e =
-            hipHostMalloc((void**)&ds.list_stats_host, list_sums * sizeof(unsigned long long), hipHostMallocDefault);
-        if (e != hipSuccess) return e;
-        memset(ds.list_stats_host, 0, list_sums * sizeof(unsigned long long));
-    }
-    if (!ds.list_stats_ev) {
-        hipError_t e = hipEventCreateWithFlags(&ds.list_stats_ev, hipEventDisableTiming);
-        if (e != hipSuccess) return e;
-    }
-    if (nlevels > 1) {
-        if (hipError_t e = make_level_counts(ds); e != hipSuccess) return e;
-    }
+    if (hipError_t e = make_list_stats(ds); e != hipSuccess) return e;
     phase_timer& T = ds.timer;
     // LDS staging of the instance tree's top (yrt_scene_set_lds_staging): the persistent walks
     // read it from LDS; the tile lists, whose walks start below it, are not built
     const bool stage = ds.lds_staging != 0 && !COUNT && PACKET;
     ds.last_lds_staging = 0;
     const float4 cam4 = make_float4(A.cam.ox, A.cam.oy, A.cam.oz, 0.0f);
-    const int stride_grid = 2048;  // grid-stride kernels: 8 blocks of 256 per CU
     if (npix_total == 0) {  // (no chunk)
         if (hipError_t e = clear_counters(counters, stream); e != hipSuccess) return e;
     }
@@ -3302,7 +3300,6 @@ hipError_t run(device_scene& ds, const dev_render_args& A, float4* out, unsigned
         chunk_args C = {pix0, (int)std::min<long long>(pix_per_chunk, npix_total - pix0), spp, tiles_x};
         if (YRT_ITEM_MAGIC) C.M = M;
         const int nsamp = C.npix * spp;
-        const int grid = (nsamp + WF_BLOCK - 1) / WF_BLOCK;
         constexpr int TB = shadow_block<PACKET>();
         const int tgrid = (nsamp + TB - 1) / TB;
         // level 0's shadow rays run on the persistent any-hit grid (k_shadow_persist) -- on
@@ -3355,134 +3352,74 @@ hipError_t run(device_scene& ds, const dev_render_args& A, float4* out, unsigned
                                        stream, ds.view, A, C, B, counters);
             }
         }
-        if (!persist) {
-            const dim3 pg((nsamp + YRT_PRIMARY_BLOCK - 1) / YRT_PRIMARY_BLOCK);
-            if (B.cam_lists)
-                hipLaunchKernelGGL((k_primary<COUNT, PACKET, SE, true>), pg, dim3(YRT_PRIMARY_BLOCK), 0, stream, ds.view,
-                                   A, C, B, counters);
-            else
-                hipLaunchKernelGGL((k_primary<COUNT, PACKET, SE, false>), pg, dim3(YRT_PRIMARY_BLOCK), 0, stream,
-                                   ds.view, A, C, B, counters);
-        }
+        if (!persist)
+            with_bool(B.cam_lists != 0, [&](auto list) {
+                hipLaunchKernelGGL((k_primary<COUNT, PACKET, SE, decltype(list)::value>),
+                                   dim3((nsamp + YRT_PRIMARY_BLOCK - 1) / YRT_PRIMARY_BLOCK), dim3(YRT_PRIMARY_BLOCK),
+                                   0, stream, ds.view, A, C, B, counters);
+            });
         T.end(t, stream);
-        // levels run: a level with no mirror rays ends the chunk's recursion. The level's
-        // k_bounce is queued before the host waits for the level's ray count, so the GPU
-        // works on it while the count comes back; only a level that turns out empty costs a
-        // launch (one k_bounce of no rays)
-        for (int level = 0; level < nlevels; level++) {
-            if (level > 0) {
-                t = T.begin(phase_bounce, stream);
-                hipLaunchKernelGGL((k_bounce<COUNT, PACKET, SE>), dim3(stride_grid), dim3(WF_BLOCK), 0, stream, ds.view,
-                                   level, B, counters);
-                T.end(t, stream);
-                bool any;
-                if (hipError_t e = level_has_rays(ds, any); e != hipSuccess) return e;
-                if (!any) break;
-            }
-            if (ds.nlights > 0) {
-                dim3 sg(level ? stride_grid * WF_BLOCK / TB : tgrid, ds.nlights);
-                if (level == 0 && shadow_persist && B.bundles) {  // the bundles' candidate lists
-                    t = T.begin(phase_lists, stream);
-                    const long long ns = (long long)super_count(nsamp) * ds.nlights;
-                    if (YRT_BUNDLE_FUSED) {
-                        hipLaunchKernelGGL(k_bundle_lists<true>, dim3((unsigned)ns), dim3(256), 0, stream, ds.view, B,
-                                           tgrid);
-                    } else {
-                        hipLaunchKernelGGL(k_bundle_super, dim3((unsigned)((ns + 3) / 4)), dim3(256), 0, stream,
-                                           ds.view, B, tgrid);
-                        const long long nw = (long long)bundle_count(nsamp) * ds.nlights;
-                        hipLaunchKernelGGL(k_bundle_lists<false>, dim3((unsigned)((nw + 3) / 4)), dim3(256), 0, stream,
-                                           ds.view, B, tgrid);
-                    }
-                    T.end(t, stream);
-                }
-                t = T.begin(phase_shadow, stream);
-                // level 0 only: at c3 the mirror levels' compacted samples trace faster with the
-                // hardware's dealing (shadow 1.64 -> 1.72 ms with them persistent)
-                if (level == 0 && shadow_persist) {
-                    // one resident grid: two 1024-thread blocks per CU (8 waves per SIMD)
-                    // (its work counters B.queue[0, 9) were zeroed by k_chunk_setup)
-                    const int nb = ds.num_cus * (YRT_SHADOW_WAVES * 4 * 64 / SP_BLOCK);
-                    constexpr int L = YRT_SHADOW_LDS_RECORDS;
-                    if (stage && L > 0 && ds.view.nwtop >= L) {  // (the copy reads L whole records)
-                        hipLaunchKernelGGL((k_shadow_persist<L>), dim3(nb), dim3(SP_BLOCK), 0, stream, ds.view,
-                                           nsamp, tgrid, B, counters, cam4);
-                        ds.last_lds_staging |= 2;
-                    }
-#if (YRT_SHADOW_SHADE_KERNEL)
-                    else if (shadow_shade)
-                        hipLaunchKernelGGL(k_shadow_shade_persist, dim3(nb), dim3(SP_BLOCK), 0, stream, ds.view, A,
-                                           nsamp, tgrid, B, counters, C, out);
-#endif
-                    else
-                        hipLaunchKernelGGL((k_shadow_persist<0>), dim3(nb), dim3(SP_BLOCK), 0, stream, ds.view,
-                                           nsamp, tgrid, B, counters, cam4);
-                } else if (!COUNT && PACKET && ds.wide_ok)
-                    hipLaunchKernelGGL((k_shadow<COUNT, PACKET, SE, true>), sg, dim3(TB), 0,
-                                       stream, ds.view, level, nsamp, B, counters, cam4);
-                else
-                    hipLaunchKernelGGL((k_shadow<COUNT, PACKET, SE, false>), sg, dim3(TB), 0,
-                                       stream, ds.view, level, nsamp, B, counters, cam4);
-                T.end(t, stream);
-            }
-            // (k_shadow_shade_persist has shaded the chunk and written its pixels)
-            if (level == 0 && shadow_shade) continue;
-            t = T.begin(phase_shade, stream);
-            const bool occ4 = ds.nlights <= 4;
-#define YRT_SHADE_LAUNCH(FU, SBV, GRID)                                                                          \
-    do {                                                                                                        \
-        if (occ4)                                                                                               \
-            hipLaunchKernelGGL((k_shade<COUNT, FU, SBV, true>), GRID, dim3(SBV), 0, stream, ds.view, A, level, nsamp, \
-                               A.max_depth, B, counters, C, out);                                               \
-        else                                                                                                    \
-            hipLaunchKernelGGL((k_shade<COUNT, FU, SBV, false>), GRID, dim3(SBV), 0, stream, ds.view, A, level,      \
-                               nsamp, A.max_depth, B, counters, C, out);                                        \
-    } while (0)
-#define YRT_SHADE_PASSES_LAUNCH(FU, GRID)                                                                          \
-    do {                                                                                                          \
-        if (occ4)                                                                                                 \
-            hipLaunchKernelGGL((k_shade_passes<FU, WF_BLOCK, true>), GRID, dim3(WF_BLOCK), 0, stream, ds.view, A, level, \
-                               nsamp, A.max_depth, B, P, counters, C);                                            \
-        else                                                                                                      \
-            hipLaunchKernelGGL((k_shade_passes<FU, WF_BLOCK, false>), GRID, dim3(WF_BLOCK), 0, stream, ds.view, A,  \
-                               level, nsamp, A.max_depth, B, P, counters, C);                                     \
-    } while (0)
-#define YRT_SHADE_GROUPS_LAUNCH(FU, GRID)                                                                          \
-    do {                                                                                                          \
-        if (occ4)                                                                                                 \
-            hipLaunchKernelGGL((k_shade_groups<FU, WF_BLOCK, true>), GRID, dim3(WF_BLOCK), 0, stream, ds.view, A, level, \
-                               nsamp, A.max_depth, B, G, counters, C);                                            \
-        else                                                                                                      \
-            hipLaunchKernelGGL((k_shade_groups<FU, WF_BLOCK, false>), GRID, dim3(WF_BLOCK), 0, stream, ds.view, A,  \
-                               level, nsamp, A.max_depth, B, G, counters, C);                                     \
-    } while (0)
-            if (groups) {
-                if constexpr (!COUNT) {  // (launch_render_wavefront_light_groups never counts work)
-                    if (fuse)
-                        YRT_SHADE_GROUPS_LAUNCH(true, dim3(grid));
-                    else
-                        YRT_SHADE_GROUPS_LAUNCH(false, dim3(level ? stride_grid : grid));
-                }
-            } else if (passes) {
-                if constexpr (!COUNT) {  // (launch_render_wavefront_passes never counts work)
-                    if (fuse)
-                        YRT_SHADE_PASSES_LAUNCH(true, dim3(grid));
-                    else
-                        YRT_SHADE_PASSES_LAUNCH(false, dim3(level ? stride_grid : grid));
-                }
-            } else if (fuse) {
-                YRT_SHADE_LAUNCH(true, WF_BLOCK, dim3(grid));
+        if (B.bundles) {  // the candidate lists of level 0's shadow items (shadow_persist, lights)
+            t = T.begin(phase_lists, stream);
+            const long long ns = (long long)super_count(nsamp) * ds.nlights;
+            if (YRT_BUNDLE_FUSED) {
+                hipLaunchKernelGGL(k_bundle_lists<true>, dim3((unsigned)ns), dim3(256), 0, stream, ds.view, B, tgrid);
             } else {
-                YRT_SHADE_LAUNCH(false, WF_BLOCK, dim3(level ? stride_grid : grid));
+                hipLaunchKernelGGL(k_bundle_super, dim3((unsigned)((ns + 3) / 4)), dim3(256), 0, stream, ds.view, B,
+                                   tgrid);
+                const long long nw = (long long)bundle_count(nsamp) * ds.nlights;
+                hipLaunchKernelGGL(k_bundle_lists<false>, dim3((unsigned)((nw + 3) / 4)), dim3(256), 0, stream,
+                                   ds.view, B, tgrid);
             }
-#undef YRT_SHADE_GROUPS_LAUNCH
-#undef YRT_SHADE_PASSES_LAUNCH
-#undef YRT_SHADE_LAUNCH
             T.end(t, stream);
-            if (level + 1 < nlevels) {
-                if (hipError_t e = fetch_level_counts(ds, B, level + 1, stream); e != hipSuccess) return e;
-            }
         }
+        // level 0 only: at c3 the mirror levels' compacted samples trace faster with the
+        // hardware's dealing (shadow 1.64 -> 1.72 ms with them persistent)
+        auto shadow0 = [&] {
+            if (!shadow_persist) return false;
+            // one resident grid: two 1024-thread blocks per CU (8 waves per SIMD)
+            // (its work counters B.queue[0, 9) were zeroed by k_chunk_setup)
+            const int nb = ds.num_cus * (YRT_SHADOW_WAVES * 4 * 64 / SP_BLOCK);
+            constexpr int L = YRT_SHADOW_LDS_RECORDS;
+            if (stage && L > 0 && ds.view.nwtop >= L) {  // (the copy reads L whole records)
+                hipLaunchKernelGGL((k_shadow_persist<L>), dim3(nb), dim3(SP_BLOCK), 0, stream, ds.view, nsamp, tgrid,
+                                   B, counters, cam4);
+                ds.last_lds_staging |= 2;
+            }
+#if (YRT_SHADOW_SHADE_KERNEL)
+            else if (shadow_shade)
+                hipLaunchKernelGGL(k_shadow_shade_persist, dim3(nb), dim3(SP_BLOCK), 0, stream, ds.view, A, nsamp,
+                                   tgrid, B, counters, C, out);
+#endif
+            else
+                hipLaunchKernelGGL((k_shadow_persist<0>), dim3(nb), dim3(SP_BLOCK), 0, stream, ds.view, nsamp, tgrid,
+                                   B, counters, cam4);
+            return true;
+        };
+        // (a fused shape has one level: its grid is level 0's)
+        auto shade = [&](int level, dim3 grid) {
+            with_bool(fuse, [&](auto fu) {
+                with_bool(ds.nlights <= 4, [&](auto occ4) {
+                    constexpr bool FU = decltype(fu)::value, OCC4 = decltype(occ4)::value;
+                    if (groups) {
+                        if constexpr (!COUNT)  // (launch_render_wavefront_light_groups never counts work)
+                            hipLaunchKernelGGL((k_shade_groups<FU, WF_BLOCK, OCC4>), grid, dim3(WF_BLOCK), 0, stream,
+                                               ds.view, A, level, nsamp, A.max_depth, B, G, counters, C);
+                    } else if (passes) {
+                        if constexpr (!COUNT)  // (launch_render_wavefront_passes never counts work)
+                            hipLaunchKernelGGL((k_shade_passes<FU, WF_BLOCK, OCC4>), grid, dim3(WF_BLOCK), 0, stream,
+                                               ds.view, A, level, nsamp, A.max_depth, B, P, counters, C);
+                    } else
+                        hipLaunchKernelGGL((k_shade<COUNT, FU, WF_BLOCK, OCC4>), grid, dim3(WF_BLOCK), 0, stream,
+                                           ds.view, A, level, nsamp, A.max_depth, B, counters, C, out);
+                });
+            });
+        };
+        // (shadow_shade: k_shadow_shade_persist has shaded the chunk and written its pixels)
+        if (hipError_t e = run_levels<COUNT, PACKET, SE>(ds, B, nlevels, nsamp, cam4, counters, stream, shadow0,
+                                                         shadow_shade, shade);
+            e != hipSuccess)
+            return e;
         if (!fuse) {
             t = T.begin(phase_accumulate, stream);
             if (groups)
@@ -3513,10 +3450,10 @@ hipError_t run(device_scene& ds, const dev_render_args& A, float4* out, unsigned
     return hipGetLastError();
 }
 
-// ---- a ray batch (yrt_shade_rays): run()'s chunk loop with the caller's rays as level 0 ----
+// ---- a ray batch (yrt_shade_rays): run()'s chunks and levels with the caller's rays as level 0 ----
 // A ray is a sample and spp is 1: chunk r0 holds rays [r0, r0 + nsamp), its sample idx is ray
 // r0 + idx. k_rays_first replaces eval_camera and the camera-relative walk; level 0's shadow
-// rays run on the plain k_shadow grid (the persistent any-hit grid's item order and the
+// rays run on the plain k_rays_shadow grid (the persistent any-hit grid's item order and the
 // bundles' boxes are laid out for pixel tiles, and no camera list exists without a common
 // origin), so the tile-list mode and the LDS staging of the handle change nothing here and the
 // handle reports neither as used. The mirror levels, the fold and the workspace are run()'s;
@@ -3524,87 +3461,44 @@ hipError_t run(device_scene& ds, const dev_render_args& A, float4* out, unsigned
 template <bool PACKET, typename SE>
 hipError_t run_rays(device_scene& ds, const dev_render_args& A, const float* rays, int n, float4* out,
                     unsigned long long* counters, hipStream_t stream) {
-    constexpr int spp = 1;
-    const int nlevels = ds.reflective ? std::max(A.max_depth, 1) : 1;
-    auto rays_for = [&](long long tgt) { return (int)std::max<long long>(1, std::min<long long>(n, tgt)); };
-    // (run()'s slots per sample record: the mirror levels' segments and their slack)
-    auto seg_of = [&](int r) { return r / level_segments + level_segments * WF_BLOCK; };
-    auto cap_of = [&](int r) { return nlevels > 1 ? level_segments * seg_of(r) : r; };
-    auto bytes_of = [&](long long tgt) { return workspace_bytes(cap_of(rays_for(tgt)), spp, ds.nlights, nlevels); };
-    const int per_chunk = rays_for(chunk_target(ds, A, bytes_of));
-    const int seg = seg_of(per_chunk);
-    const int cap = cap_of(per_chunk);
-    if (hipError_t e = grow_workspace(ds, workspace_bytes(cap, spp, ds.nlights, nlevels)); e != hipSuccess) return e;
-    wf_buffers B = carve(ds.work, cap, spp, ds.nlights, nlevels);
-    B.seg = seg;
-    B.need_v = ds.view.ntextures > 0;
+    chunk_plan plan;
+    if (hipError_t e = plan_chunks(ds, A, n, 1, 1, nullptr, nullptr, plan); e != hipSuccess) return e;
+    wf_buffers& B = plan.B;
     ds.last_camera_lists = ds.last_bundles = false;
     ds.last_lds_staging = 0;
-    if (nlevels > 1) {
-        if (hipError_t e = make_level_counts(ds); e != hipSuccess) return e;
-    }
     phase_timer& T = ds.timer;
     const float4 cam4 = make_float4(0.0f, 0.0f, 0.0f, 0.0f);  // (no level takes its view point from a camera)
-    const int stride_grid = 2048;
     constexpr int TB = shadow_block<PACKET>();
-    const bool wide = PACKET && ds.wide_ok;
-    const bool occ4 = ds.nlights <= 4;
     const float3 amb3 = make_float3(A.amb[0], A.amb[1], A.amb[2]);
-    for (long long r0 = 0; r0 < n; r0 += per_chunk) {
-        const int nsamp = (int)std::min<long long>(per_chunk, n - r0);
-        const int grid = (nsamp + WF_BLOCK - 1) / WF_BLOCK;
-        const int tgrid = (nsamp + TB - 1) / TB;
+    for (long long r0 = 0; r0 < n; r0 += plan.per_chunk) {
+        const int nsamp = (int)std::min<long long>(plan.per_chunk, n - r0);
         B.rays = rays + (size_t)r0 * 8;
         B.rad = reinterpret_cast<f4*>(out + r0);
         int t = T.begin(phase_lists, stream);
-        launch_chunk_setup(ds, B, 0, cam4, nullptr, nlevels, counters, r0 == 0, stream);  // (no camera-relative records)
+        launch_chunk_setup(ds, B, 0, cam4, nullptr, plan.nlevels, counters, r0 == 0, stream);  // (no camera-relative records)
         T.end(t, stream);
         t = T.begin(phase_primary, stream);
-        hipLaunchKernelGGL((k_rays_first<PACKET, SE>), dim3(grid), dim3(WF_BLOCK), 0, stream, ds.view, nsamp, B,
-                           counters);
+        hipLaunchKernelGGL((k_rays_first<PACKET, SE>), dim3((nsamp + WF_BLOCK - 1) / WF_BLOCK), dim3(WF_BLOCK), 0,
+                           stream, ds.view, nsamp, B, counters);
         T.end(t, stream);
-        for (int level = 0; level < nlevels; level++) {  // (run()'s level loop)
-            if (level > 0) {
-                t = T.begin(phase_bounce, stream);
-                hipLaunchKernelGGL((k_bounce<false, PACKET, SE>), dim3(stride_grid), dim3(WF_BLOCK), 0, stream, ds.view,
-                                   level, B, counters);
-                T.end(t, stream);
-                bool any;
-                if (hipError_t e = level_has_rays(ds, any); e != hipSuccess) return e;
-                if (!any) break;
-            }
-            if (ds.nlights > 0) {
-                const dim3 sg(level ? stride_grid * WF_BLOCK / TB : tgrid, ds.nlights);
-                t = T.begin(phase_shadow, stream);
-                if constexpr (PACKET) {
-                    if (wide && level)
-                        hipLaunchKernelGGL((k_shadow<false, true, SE, true>), sg, dim3(TB), 0, stream, ds.view, level,
-                                           nsamp, B, counters, cam4);
-                    else if (wide)
-                        hipLaunchKernelGGL((k_rays_shadow<true, SE, true>), sg, dim3(TB), 0, stream, ds.view, nsamp, B,
-                                           counters);
-                }
-                if (!wide && level)
-                    hipLaunchKernelGGL((k_shadow<false, PACKET, SE, false>), sg, dim3(TB), 0, stream, ds.view, level,
-                                       nsamp, B, counters, cam4);
-                else if (!wide)
-                    hipLaunchKernelGGL((k_rays_shadow<PACKET, SE, false>), sg, dim3(TB), 0, stream, ds.view, nsamp, B,
-                                       counters);
-                T.end(t, stream);
-            }
-            t = T.begin(phase_shade, stream);
-            const dim3 hg(level ? stride_grid : grid);
-            if (occ4)
-                hipLaunchKernelGGL(k_rays_shade<true>, hg, dim3(WF_BLOCK), 0, stream, ds.view, amb3, level, nsamp,
-                                   A.max_depth, B, counters);
-            else
-                hipLaunchKernelGGL(k_rays_shade<false>, hg, dim3(WF_BLOCK), 0, stream, ds.view, amb3, level, nsamp,
-                                   A.max_depth, B, counters);
-            T.end(t, stream);
-            if (level + 1 < nlevels) {
-                if (hipError_t e = fetch_level_counts(ds, B, level + 1, stream); e != hipSuccess) return e;
-            }
-        }
+        auto shadow0 = [&] {
+            with_bool(PACKET && ds.wide_ok, [&](auto wide) {
+                constexpr bool WIDE = PACKET && decltype(wide)::value;  // (no wide per-lane walk)
+                hipLaunchKernelGGL((k_rays_shadow<PACKET, SE, WIDE>), dim3((nsamp + TB - 1) / TB, ds.nlights),
+                                   dim3(TB), 0, stream, ds.view, nsamp, B, counters);
+            });
+            return true;
+        };
+        auto shade = [&](int level, dim3 grid) {
+            with_bool(ds.nlights <= 4, [&](auto occ4) {
+                hipLaunchKernelGGL(k_rays_shade<decltype(occ4)::value>, grid, dim3(WF_BLOCK), 0, stream, ds.view, amb3,
+                                   level, nsamp, A.max_depth, B, counters);
+            });
+        };
+        if (hipError_t e = run_levels<false, PACKET, SE>(ds, B, plan.nlevels, nsamp, cam4, counters, stream, shadow0,
+                                                         false, shade);
+            e != hipSuccess)
+            return e;
     }
     return hipGetLastError();
 }
@@ -3614,27 +3508,21 @@ hipError_t run_rays(device_scene& ds, const dev_render_args& A, const float* ray
 hipError_t launch_shade_rays_wavefront(device_scene& ds, const dev_render_args& args, const float* rays, int n,
                                        void* out_rgba, unsigned long long* counters, bool packet, hipStream_t stream) {
     if (n <= 0) return clear_counters(counters, stream);  // (no chunk)
-    float4* out = (float4*)out_rgba;
-    if (packet) return run_rays<true, uint32_t>(ds, args, rays, n, out, counters, stream);
-    if (ds.narrow_stack) return run_rays<false, uint16_t>(ds, args, rays, n, out, counters, stream);
-    return run_rays<false, uint32_t>(ds, args, rays, n, out, counters, stream);
+    return with_walk(ds, packet, [&](auto pk, auto se) {
+        return run_rays<decltype(pk)::value, decltype(se)>(ds, args, rays, n, (float4*)out_rgba, counters, stream);
+    });
 }
 
 hipError_t launch_render_wavefront(device_scene& ds, const dev_render_args& args, void* out_rgba,
                                    unsigned long long* counters, bool count_work, bool packet, hipStream_t stream) {
     // an empty window (a band offset without bands): no chunk
     if (args.tile_w <= 0 || args.tile_h <= 0) return clear_counters(counters, stream);
-    float4* out = (float4*)out_rgba;
-    if (packet) {
-        // the per-wave stack holds 32-bit node indices: no narrow/wide split needed
-        return count_work ? run<true, true, uint32_t>(ds, args, out, counters, stream)
-                          : run<false, true, uint32_t>(ds, args, out, counters, stream);
-    }
-    if (ds.narrow_stack)
-        return count_work ? run<true, false, uint16_t>(ds, args, out, counters, stream)
-                          : run<false, false, uint16_t>(ds, args, out, counters, stream);
-    return count_work ? run<true, false, uint32_t>(ds, args, out, counters, stream)
-                      : run<false, false, uint32_t>(ds, args, out, counters, stream);
+    return with_walk(ds, packet, [&](auto pk, auto se) {
+        return with_bool(count_work, [&](auto count) {
+            return run<decltype(count)::value, decltype(pk)::value, decltype(se)>(ds, args, (float4*)out_rgba, counters,
+                                                                                  stream);
+        });
+    });
 }
 
 hipError_t launch_render_wavefront_passes(device_scene& ds, const dev_render_args& args, unsigned mask,
@@ -3645,10 +3533,9 @@ hipError_t launch_render_wavefront_passes(device_scene& ds, const dev_render_arg
     P.mask = (mask & ((1u << pass_count) - 1)) | (beauty_rgba ? 1u << pass_count : 0u);
     for (int k = 0; k < pass_count; k++) P.out[k] = (mask >> k & 1) ? (float4*)out.plane[k] : nullptr;
     P.out[pass_count] = (float4*)beauty_rgba;
-    float4* beauty = (float4*)beauty_rgba;
-    if (packet) return run<false, true, uint32_t>(ds, args, beauty, counters, stream, &P);
-    if (ds.narrow_stack) return run<false, false, uint16_t>(ds, args, beauty, counters, stream, &P);
-    return run<false, false, uint32_t>(ds, args, beauty, counters, stream, &P);
+    return with_walk(ds, packet, [&](auto pk, auto se) {
+        return run<false, decltype(pk)::value, decltype(se)>(ds, args, (float4*)beauty_rgba, counters, stream, &P);
+    });
 }
 
 // The planes in the kernels' order: the groups, then the ambient plane and the beauty where
@@ -3679,9 +3566,9 @@ hipError_t launch_render_wavefront_light_groups(device_scene& ds, const dev_rend
         G.out[G.nplanes++] = (float4*)out.beauty;
     }
     for (int k = G.nplanes; k <= group_planes; k++) tab[k] = (int)tab.size() - (group_planes + 1);
-    if (packet) return run<false, true, uint32_t>(ds, args, nullptr, counters, stream, nullptr, &G);
-    if (ds.narrow_stack) return run<false, false, uint16_t>(ds, args, nullptr, counters, stream, nullptr, &G);
-    return run<false, false, uint32_t>(ds, args, nullptr, counters, stream, nullptr, &G);
+    return with_walk(ds, packet, [&](auto pk, auto se) {
+        return run<false, decltype(pk)::value, decltype(se)>(ds, args, nullptr, counters, stream, nullptr, &G);
+    });
 }
 
 }  // namespace yrt
