@@ -2008,15 +2008,85 @@ __global__ __launch_bounds__(SP_BLOCK, YRT_SHADOW_WAVES) void k_shadow_persist(d
 // material, the textures, the lights that are not occluded, the mirror branch. Every kernel
 // that shades calls this one body (k_shade, k_rays_shade, k_shade_passes and
 // k_shadow_shade_persist's epilogue): the image, the ray batches and the passes are bit-exact
-// because they run the same operations in the same order. (Two kernels write these statements
-// out in a body of their own and are to be changed with this one: the fused k_shade_passes, and
-// k_shade_groups, whose light loop runs once per plane over the plane's lights.)
+// because they run the same operations in the same order. Two kernels keep a body of their own:
+// the fused k_shade_passes, and k_shade_groups, whose light loop runs once per plane over the
+// plane's lights. The three bodies call one light_reach, one light_term and (the two with
+// mirror levels) one compact_mirror_rays. What still stands in each of them, and is to be
+// changed in all three together: the surface and material block ahead of the light loop (s1, uv,
+// the material rows, the texels, la), v, the light's occlusion test, `c = c + (ld + ls)`, and
+// the `!reflective` / depth-cap / spawn arithmetic after the loop. (As one function that block
+// gave the unfused k_shade three more VGPRs and every k_shade_groups other instructions.)
 // OCC4: the lights' occlusion is the mask occ_bits, else the bytes B.occl.
 // LATE (k_shadow_shade_persist, at the any-hit grid's 64 VGPRs): what only the end needs, la and
 // kr and the reflective flag, is computed or loaded again after the light loop instead of held
 // across it; the same operations on the same values, 7 VGPR spills fewer.
 // TERMS (the shading passes, k_shade_passes): *terms collects the terms the beauty adds up, as
 // they are computed; with the default, an empty type, nothing of it is compiled.
+// The straight-line pieces the three shading bodies share (shade_hit, the fused k_shade_passes,
+// k_shade_groups). Inlined, they leave every shading kernel its count of instructions per
+// mnemonic and its registers, spills and LDS; a few instructions stand elsewhere or have a
+// commutative operation's operands swapped ("Shared shading pieces", and
+// `tools/isa_dump.py --compare` for the check).
+// light_reach: light record `lr` (six rows, the same for every lane: one scalar fetch instead of
+// six 64-lane vector loads of one address) seen from p: direction l, distance r, emission ke
+__device__ __forceinline__ void light_reach(const f4* lr, vec3f p, vec3f& l, float& r, vec3f& ke) {
+    float4 lrec[6];
+    ld_scalar<6>(lr, lrec);
+    frame3f lf = {xyz(lrec[0]), xyz(lrec[1]), xyz(lrec[2]), xyz(lrec[3])};
+    vec3f lp0 = xyz(lrec[4]);
+    ke = xyz(lrec[5]);
+    vec3f tp = transform_point(lf, lp0 - p);
+    normalize_len(tp, l, r);
+}
+// light_term: one light's diffuse and specular terms ld, ls (raytrace.cpp:147-185) from the
+// view direction v, the light's {l, r, ke} and the material's kd, ks, ns
+__device__ __forceinline__ void light_term(int kind, vec3f nrm, vec3f v, vec3f l, float r, vec3f ke, vec3f kd,
+                                           vec3f ks, float ns, vec3f& ld, vec3f& ls) {
+    vec3f h;
+    float hlen;
+    normalize_len(v + l, h, hlen);
+    const vec3f ker = div3(ke, r * r);
+    ld = kd * ker;
+    ls = ks * ker;
+    if (kind == kind_lines) {
+        float prodnl = dot(nrm, l);
+        float prodnh = dot(nrm, h);
+        if (prodnl < 0.0f) prodnl *= -1;
+        if (prodnh < 0.0f) prodnh *= -1;
+        float sinnl = __builtin_sqrtf(1.0f - prodnl);
+        float sinnh = __builtin_sqrtf(1.0f - prodnh);
+        ld = ld * sinnl;
+        ls = ls * spec_pow(sinnh, ns, ls);
+    } else {
+        ld = ld * smax(0.0f, dot(nrm, l));
+        ls = ls * spec_pow(smax(0.0f, dot(nrm, h)), ns, ls);
+    }
+}
+// compact_mirror_rays: the block's mirror rays (spawn; mask its wave's ballot) take consecutive
+// slots of segment gout of level + 1 (waves in wave order, lanes in lane order) behind one
+// atomic per block. (One atomic per wave: c3 shade 1.99 -> 5.81 ms.) The fold follows parent
+// indices, so the order is free. Every lane of the block calls it: two barriers.
+template <int SB>
+__device__ __forceinline__ void compact_mirror_rays(const wf_buffers& B, int level, int gout, int idx, bool spawn,
+                                                    unsigned long long mask, vec3f p, vec3f dr,
+                                                    int (&cmp_count)[SB / 64], int (&cmp_base)[SB / 64]) {
+    const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    if (lane == 0) cmp_count[w] = __popcll(mask);
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        int tot = 0;
+        for (int q = 0; q < SB / 64; q++) tot += cmp_count[q];
+        int acc = tot ? atomicAdd(seg_counter(B.count, level + 1, gout), tot) : 0;
+        for (int q = 0; q < SB / 64; q++) cmp_base[q] = acc, acc += cmp_count[q];
+    }
+    __syncthreads();
+    if (spawn) {
+        const int slot = gout * B.seg + cmp_base[w] + __popcll(mask & ((1ull << lane) - 1));
+        B.ray_o(level + 1)[slot] = {p.x, p.y, p.z, __int_as_float(idx)};
+        B.ray_d(level + 1)[slot] = {dr.x, dr.y, dr.z, 0};
+    }
+}
+
 struct no_terms {};
 struct pass_terms {
     // c after the light loop, its ld and ls parts, the vector added for the mirror ray where
@@ -2073,10 +2143,8 @@ __device__ __forceinline__ void shade_hit(const dev_scene_view& S, const wf_buff
     for (int li = 0; li < S.nlights; li++) {
         if (OCC4 ? ((occ_bits >> li) & 1u) != 0u : ldb(B.occl + (size_t)li * B.capacity + idx) != 0) continue;
         const f4* lr = S.lights + 6 * li;
-        // the light record is the same for every lane (li is the loop index):
-        // one scalar fetch instead of six 64-lane vector loads of one address
-        vec3f l, h, ke;
-        float r, hlen;
+        vec3f l, ke;
+        float r;
         if (carried && li < ncarried) {
             // (YRT_LIGHT_CARRY) the light step of this item left the sample's {l, r} in LDS
             float4 lrec[2];
@@ -2085,34 +2153,13 @@ __device__ __forceinline__ void shade_hit(const dev_scene_view& S, const wf_buff
             const float4 c4 = carried[li * 64];
             l = xyz(c4), r = c4.w;
         } else {
-            float4 lrec[6];
-            ld_scalar<6>(lr, lrec);
-            frame3f lf = {xyz(lrec[0]), xyz(lrec[1]), xyz(lrec[2]), xyz(lrec[3])};
-            vec3f lp0 = xyz(lrec[4]);
-            ke = xyz(lrec[5]);
-            vec3f tp = transform_point(lf, lp0 - p);
-            normalize_len(tp, l, r);
+            light_reach(lr, p, l, r, ke);
         }
-        normalize_len(v + l, h, hlen);
         vec3f kd = kd0, ks = ks0;
         if (kd_txt >= 0) kd = kd * tkd;
         if (ks_txt >= 0) ks = ks * tks;
-        const vec3f ker = div3(ke, r * r);
-        vec3f ld = kd * ker;
-        vec3f ls = ks * ker;
-        if (kind == kind_lines) {
-            float prodnl = dot(nrm, l);
-            float prodnh = dot(nrm, h);
-            if (prodnl < 0.0f) prodnl *= -1;
-            if (prodnh < 0.0f) prodnh *= -1;
-            float sinnl = __builtin_sqrtf(1.0f - prodnl);
-            float sinnh = __builtin_sqrtf(1.0f - prodnh);
-            ld = ld * sinnl;
-            ls = ls * spec_pow(sinnh, ns, ls);
-        } else {
-            ld = ld * smax(0.0f, dot(nrm, l));
-            ls = ls * spec_pow(smax(0.0f, dot(nrm, h)), ns, ls);
-        }
+        vec3f ld, ls;
+        light_term(kind, nrm, v, l, r, ke, kd, ks, ns, ld, ls);
         c = c + (ld + ls);
         if constexpr (SPLIT) terms->d = terms->d + ld, terms->s = terms->s + ls;
     }
@@ -2174,6 +2221,40 @@ __device__ __forceinline__ void sum_pixels(const dev_render_args& A, const chunk
                 v = acc / float(spp);
             }
             float* o = reinterpret_cast<float*>(out + (size_t)ly * A.out_stride + lx);
+            o[comp] = v;
+            if (comp == 0) o[3] = valid ? 1.0f : 0.0f;
+        }
+    }
+}
+
+// the fused shapes' per-pixel sums over several planes: the block's per-sample values stand in
+// LDS rows of SB + 1 floats per (plane, component), a pixel's samples consecutive; one lane per
+// (pixel, plane, colour component), each lane's sum the reference's ordered chain of adds for
+// that component. NP: the plane count, an int or (its divisions by a constant)
+// std::integral_constant; plane k is summed into out(k) where wanted(k). Both are callables that
+// read the kernel's argument where it is used, as accumulate_plane's are: with the mask by value
+// and the planes as a pointer the fused k_shade_passes came out two and three instructions longer
+template <int SB, class NP, class WANTED, class OUT>
+__device__ __forceinline__ void sum_plane_rows(const dev_render_args& A, const chunk_args& C, const float* rows,
+                                               NP nplanes, WANTED&& wanted, OUT&& out) {
+    constexpr int ROW = SB + 1;
+    const int ppb = SB / C.spp;
+    for (int t = (int)threadIdx.x; t < 3 * nplanes * ppb; t += SB) {
+        const int px = t / (3 * nplanes), r = t - 3 * nplanes * px;
+        const int k = r / 3, comp = r - 3 * k;
+        if (!wanted(k)) continue;
+        const int pl = (int)(blockIdx.x * SB / C.spp) + px;
+        int lx, ly, i, j;
+        const bool valid = pl < C.npix && pixel_of(A, C, C.pix0 + pl, lx, ly, i, j);
+        if (pl < C.npix && lx < A.tile_w && ly < A.tile_h) {
+            float v = 0.0f;
+            if (valid) {
+                const float* row = rows + (k * 3 + comp) * ROW + px * C.spp;
+                float acc = 0.0f;
+                for (int q = 0; q < C.spp; q++) acc = acc + row[q];
+                v = acc / float(C.spp);
+            }
+            float* o = reinterpret_cast<float*>(out(k) + (size_t)ly * A.out_stride + lx);
             o[comp] = v;
             if (comp == 0) o[3] = valid ? 1.0f : 0.0f;
         }
@@ -2252,6 +2333,8 @@ __device__ __forceinline__ void shade_samples(dev_scene_view S, dev_render_args 
             float4 s0 = ld4s(B.surf0 + idx);
             uint32_t occ_bits = 0;
             if constexpr (OCC4) {
+                // (the same text in the fused k_shade_passes; as a function it gave every OCC4
+                // kernel other instructions)
 #pragma unroll
                 for (int q = 0; q < 4; q++) {
                     const int lq = q < S.nlights ? q : 0;  // an unconditional load, masked after
@@ -2318,31 +2401,15 @@ __device__ __forceinline__ void shade_samples(dev_scene_view S, dev_render_args 
                 B.rad[node] = {col.x, col.y, col.z, 1.0f};
             }
         }
-        // compaction of the mirror rays (the fold follows parent indices, so the order is
-        // free): a sample's own fold records go out at once; the block's mirror rays take
-        // consecutive slots of its segment (waves in wave order, lanes in lane order)
-        // behind one atomic per block. (One atomic per wave: c3 shade 1.99 -> 5.81 ms.)
+        // the mirror rays: a sample's own fold records go out at once, its ray is compacted
+        // into the next level's segment
         if constexpr (FUSE) continue;  // one level: no mirror rays
         const unsigned long long mask = __ballot(spawn);
-        const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
         if (spawn) {
             B.rec0(level)[idx] = {rec_d.x, rec_d.y, rec_d.z, __int_as_float(rec_mat)};
             B.rec1(level)[idx] = {rec_la.x, rec_la.y, rec_la.z, 0};
         }
-        if (lane == 0) cmp_count[w] = __popcll(mask);
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            int tot = 0;
-            for (int q = 0; q < SB / 64; q++) tot += cmp_count[q];
-            int acc = tot ? atomicAdd(seg_counter(B.count, level + 1, gout), tot) : 0;
-            for (int q = 0; q < SB / 64; q++) cmp_base[q] = acc, acc += cmp_count[q];
-        }
-        __syncthreads();
-        if (spawn) {
-            const int slot = gout * B.seg + cmp_base[w] + __popcll(mask & ((1ull << lane) - 1));
-            B.ray_o(level + 1)[slot] = {p.x, p.y, p.z, __int_as_float(idx)};
-            B.ray_d(level + 1)[slot] = {dr.x, dr.y, dr.z, 0};
-        }
+        compact_mirror_rays<SB>(B, level, gout, idx, spawn, mask, p, dr, cmp_count, cmp_base);
     }
     }
     if (FUSE) {
@@ -2379,12 +2446,13 @@ __global__ __launch_bounds__(WF_BLOCK, YRT_SHADE_LEVEL_WAVES) void k_rays_shade(
 }
 
 // the shading passes (yrt_render_passes). Unfused (mirror levels, or pixels that are not whole
-// in a block): shade_samples. Fused: a body of its own, with shade_hit's arithmetic written out
-// and the two more accumulators (d, s) beside c. Through shade_hit's TERMS the fused kernel was
-// measurably slower, and so was this body with small changes of form: its own sRGB
-// staging (not stage_srgb) and the loop over its one segment are what keeps the compiler's
-// output. A change to shade_hit is to be made here too (tests/test_gpu_passes*.py compare its
-// beauty with k_shade's bit for bit).
+// in a block): shade_samples. Fused: a body of its own, with the two more accumulators (d, s)
+// beside c. Through shade_hit's TERMS the fused kernel was measurably slower, and
+// so was this body with small changes of form: its own sRGB staging (not stage_srgb) and the
+// loop over its one segment are what keeps the compiler's output. It shares light_reach and
+// light_term with shade_hit and sum_plane_rows with k_shade_groups; the statements listed at
+// shade_hit and the OCC4 gather (shade_samples') are written out here and change with theirs
+// (tests/test_gpu_passes*.py compare its beauty with k_shade's bit for bit).
 // Fused: 70-72 VGPRs and no scratch; at k_shade's 7 waves d and s put 32 bytes per lane into
 // scratch
 constexpr int shade_pass_waves = 6;
@@ -2465,35 +2533,14 @@ __global__ __launch_bounds__(SB, FUSE ? shade_pass_waves : YRT_SHADE_LEVEL_WAVES
                 normalize_len(ro - p, v, vlen);
                 for (int li = 0; li < S.nlights; li++) {
                     if (OCC4 ? ((occ_bits >> li) & 1u) != 0u : ldb(B.occl + (size_t)li * B.capacity + idx) != 0) continue;
-                    const f4* lr = S.lights + 6 * li;
-                    float4 lrec[6];
-                    ld_scalar<6>(lr, lrec);
-                    frame3f lf = {xyz(lrec[0]), xyz(lrec[1]), xyz(lrec[2]), xyz(lrec[3])};
-                    vec3f lp0 = xyz(lrec[4]), ke = xyz(lrec[5]);
-                    vec3f tp = transform_point(lf, lp0 - p);
-                    vec3f l, h;
-                    float r, hlen;
-                    normalize_len(tp, l, r);
-                    normalize_len(v + l, h, hlen);
+                    vec3f l, ke;
+                    float r;
+                    light_reach(S.lights + 6 * li, p, l, r, ke);
                     vec3f kd = kd0, ks = ks0;
                     if (kd_txt >= 0) kd = kd * tkd;
                     if (ks_txt >= 0) ks = ks * tks;
-                    const vec3f ker = div3(ke, r * r);
-                    vec3f ld = kd * ker;
-                    vec3f ls = ks * ker;
-                    if (kind == kind_lines) {
-                        float prodnl = dot(nrm, l);
-                        float prodnh = dot(nrm, h);
-                        if (prodnl < 0.0f) prodnl *= -1;
-                        if (prodnh < 0.0f) prodnh *= -1;
-                        float sinnl = __builtin_sqrtf(1.0f - prodnl);
-                        float sinnh = __builtin_sqrtf(1.0f - prodnh);
-                        ld = ld * sinnl;
-                        ls = ls * spec_pow(sinnh, ns, ls);
-                    } else {
-                        ld = ld * smax(0.0f, dot(nrm, l));
-                        ls = ls * spec_pow(smax(0.0f, dot(nrm, h)), ns, ls);
-                    }
+                    vec3f ld, ls;
+                    light_term(kind, nrm, v, l, r, ke, kd, ks, ns, ld, ls);
                     c = c + (ld + ls);
                     cd = cd + ld;
                     cs = cs + ls;
@@ -2528,27 +2575,9 @@ __global__ __launch_bounds__(SB, FUSE ? shade_pass_waves : YRT_SHADE_LEVEL_WAVES
         // raytrace.cpp:232-249 per plane: one lane per (pixel, plane, colour component), each
         // lane's sum the reference's ordered chain of adds for that component
         __syncthreads();
-        const int ppb = SB / C.spp;
-        for (int t = (int)threadIdx.x; t < 3 * pass_planes * ppb; t += SB) {
-            const int px = t / (3 * pass_planes), r = t - 3 * pass_planes * px;
-            const int k = r / 3, comp = r - 3 * k;
-            if (!(P.mask >> k & 1)) continue;
-            const int pl = (int)(blockIdx.x * SB / C.spp) + px;
-            int lx, ly, i, j;
-            const bool valid = pl < C.npix && pixel_of(A, C, C.pix0 + pl, lx, ly, i, j);
-            if (pl < C.npix && lx < A.tile_w && ly < A.tile_h) {
-                float v = 0.0f;
-                if (valid) {
-                    const float* row = fused + (k * 3 + comp) * ROW + px * C.spp;
-                    float acc = 0.0f;
-                    for (int q = 0; q < C.spp; q++) acc = acc + row[q];
-                    v = acc / float(C.spp);
-                }
-                float* o = reinterpret_cast<float*>(P.out[k] + (size_t)ly * A.out_stride + lx);
-                o[comp] = v;
-                if (comp == 0) o[3] = valid ? 1.0f : 0.0f;
-            }
-        }
+        sum_plane_rows<SB>(
+            A, C, fused, std::integral_constant<int, pass_planes>{}, [&](int k) { return P.mask >> k & 1; },
+            [&](int k) { return P.out[k]; });
     }
     flush(counters, cnt_depth_truncated, truncated);
 }
@@ -2570,7 +2599,10 @@ __global__ __launch_bounds__(SB, FUSE ? shade_pass_waves : YRT_SHADE_LEVEL_WAVES
 // -0 (it ends in an addition to c, which starts at +0), so the bits are the same; level 0's
 // `+ la` and the `0 * kr` of a cut mirror ray are computed as written.
 // k_shade_groups has a body of its own, like the fused k_shade_passes: shade_hit keeps one c
-// per call. A change to shade_hit is to be made here too (tests/test_gpu_light_groups.py
+// per call. It shares light_reach, light_term and compact_mirror_rays with shade_hit and
+// shade_samples, and sum_plane_rows with the fused k_shade_passes; the statements listed at
+// shade_hit are written out here (kd and ks once per sample, the spawn ahead of the planes) and
+// change with theirs, and the fold is shade_samples' per plane (tests/test_gpu_light_groups.py
 // compares every plane with yrt_render of its variant bit for bit).
 struct group_buffers {  // (group_planes planes: wf_workspace.h)
     int nplanes;              // planes in use, [0, nplanes)
@@ -2631,7 +2663,8 @@ __global__ __launch_bounds__(SB, shade_group_waves) void k_shade_groups(dev_scen
             const float4 s0 = ld4s(B.surf0 + idx);
             if constexpr (OCC4) {
                 // (four unconditional loads, a light past the scene's reading light 0's byte;
-                // only the bits of the plane's own lights are looked at)
+                // only the bits of the plane's own lights are looked at, so no `q < S.nlights`
+                // mask as in shade_samples' gather: with it the kernel has other instructions)
 #pragma unroll
                 for (int q = 0; q < 4; q++) {
                     const int lq = q < S.nlights ? q : 0;
@@ -2695,31 +2728,10 @@ __global__ __launch_bounds__(SB, shade_group_waves) void k_shade_groups(dev_scen
                 for (int q = q0; q < q1; q++) {
                     const int li = __builtin_amdgcn_readfirstlane(order[q]);
                     if (OCC4 ? ((occ_bits >> li) & 1u) != 0u : ldb(B.occl + (size_t)li * B.capacity + idx) != 0) continue;
-                    float4 lrec[6];
-                    ld_scalar<6>(S.lights + 6 * li, lrec);
-                    frame3f lf = {xyz(lrec[0]), xyz(lrec[1]), xyz(lrec[2]), xyz(lrec[3])};
-                    vec3f lp0 = xyz(lrec[4]), ke = xyz(lrec[5]);
-                    vec3f tp = transform_point(lf, lp0 - p);
-                    vec3f l, h;
-                    float r, hlen;
-                    normalize_len(tp, l, r);
-                    normalize_len(v + l, h, hlen);
-                    const vec3f ker = div3(ke, r * r);
-                    vec3f ld = kd * ker;
-                    vec3f ls = ks * ker;
-                    if (kind == kind_lines) {
-                        float prodnl = dot(nrm, l);
-                        float prodnh = dot(nrm, h);
-                        if (prodnl < 0.0f) prodnl *= -1;
-                        if (prodnh < 0.0f) prodnh *= -1;
-                        float sinnl = __builtin_sqrtf(1.0f - prodnl);
-                        float sinnh = __builtin_sqrtf(1.0f - prodnh);
-                        ld = ld * sinnl;
-                        ls = ls * spec_pow(sinnh, ns, ls);
-                    } else {
-                        ld = ld * smax(0.0f, dot(nrm, l));
-                        ls = ls * spec_pow(smax(0.0f, dot(nrm, h)), ns, ls);
-                    }
+                    vec3f l, ke, ld, ls;
+                    float r;
+                    light_reach(S.lights + 6 * li, p, l, r, ke);
+                    light_term(kind, nrm, v, l, r, ke, kd, ks, ns, ld, ls);
                     c = c + (ld + ls);
                 }
                 const vec3f lak = ambk ? la : la0;
@@ -2754,50 +2766,17 @@ __global__ __launch_bounds__(SB, shade_group_waves) void k_shade_groups(dev_scen
             }
         }
         if constexpr (FUSE) continue;  // one level: no mirror rays
-        // the mirror rays, spawned and compacted once for all planes (shade_samples' compaction)
+        // the mirror rays, spawned and compacted once for all planes
         const unsigned long long mask = __ballot(spawn);
-        const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
         if (spawn) B.rec1(level)[idx] = {la.x, la.y, la.z, 0};
-        if (lane == 0) cmp_count[w] = __popcll(mask);
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            int tot = 0;
-            for (int q = 0; q < SB / 64; q++) tot += cmp_count[q];
-            int acc = tot ? atomicAdd(seg_counter(B.count, level + 1, gout), tot) : 0;
-            for (int q = 0; q < SB / 64; q++) cmp_base[q] = acc, acc += cmp_count[q];
-        }
-        __syncthreads();
-        if (spawn) {
-            const int slot = gout * B.seg + cmp_base[w] + __popcll(mask & ((1ull << lane) - 1));
-            B.ray_o(level + 1)[slot] = {p.x, p.y, p.z, __int_as_float(idx)};
-            B.ray_d(level + 1)[slot] = {dr.x, dr.y, dr.z, 0};
-        }
+        compact_mirror_rays<SB>(B, level, gout, idx, spawn, mask, p, dr, cmp_count, cmp_base);
     }
     }
     if (FUSE) {
         // raytrace.cpp:232-249 per plane: one lane per (pixel, plane, colour component), each
         // lane's sum the reference's ordered chain of adds for that component
         __syncthreads();
-        const int ppb = SB / C.spp;
-        for (int e = (int)threadIdx.x; e < 3 * nplanes * ppb; e += SB) {
-            const int px = e / (3 * nplanes), r = e - 3 * nplanes * px;
-            const int k = r / 3, comp = r - 3 * k;
-            const int pl = (int)(blockIdx.x * SB / C.spp) + px;
-            int lx, ly, i, j;
-            const bool valid = pl < C.npix && pixel_of(A, C, C.pix0 + pl, lx, ly, i, j);
-            if (pl < C.npix && lx < A.tile_w && ly < A.tile_h) {
-                float val = 0.0f;
-                if (valid) {
-                    const float* row = fused + (k * 3 + comp) * ROW + px * C.spp;
-                    float acc = 0.0f;
-                    for (int q = 0; q < C.spp; q++) acc = acc + row[q];
-                    val = acc / float(C.spp);
-                }
-                float* o = reinterpret_cast<float*>(G.out[k] + (size_t)ly * A.out_stride + lx);
-                o[comp] = val;
-                if (comp == 0) o[3] = valid ? 1.0f : 0.0f;
-            }
-        }
+        sum_plane_rows<SB>(A, C, fused, nplanes, [](int) { return true; }, [&](int k) { return G.out[k]; });
     }
     flush(counters, cnt_depth_truncated, truncated);
 }
