@@ -522,6 +522,81 @@ int  yrt_render_ao(yrt_scene* ds, const yrt_render_params* p, const yrt_ao_param
 /* per shape its primitive kind: 0 triangles, 1 lines, 2 points, 3 empty; n always set; kind may be NULL */
 int  yrt_host_scene_shape_kinds(const yrt_host_scene* hs, int* kind, int cap, int* n);
 
+/* ---- camera models: thin-lens depth of field, orthographic, panorama ----
+ * yrt_render traces eval_camera's pinhole rays. These two calls generate the camera rays of
+ * another model on the device, and the first also shades them as ray batches (yrt_shade_rays'
+ * pipeline) and box-filters the colours, so no ray and no per-ray colour crosses the host.
+ * Notation: W x H the image, (i, j) the image pixel (not the window's), ns = p->samples,
+ * q = jj*ns + ii, u = (i + (ii + 0.5f)/ns)/W and v = (j + (jj + 0.5f)/ns)/H as in yrt_render.
+ * cam is the scene camera p->camera with its focus replaced by `focus` when that is > 0:
+ * o, x, y (the frame's y * -1), z, h = 2*focus*tanf(fovy/2), w = h*aspect, focus. All
+ * arithmetic is float32, left to right as written, with no contraction; every ray has
+ * tmin = 1e-4f (the camera rays') and tmax = FLT_MAX; `.c` is each of x, y, z; normalize(a) is
+ * a * (1 / sqrtf(a.x*a.x + a.y*a.y + a.z*a.z)), a itself at length 0.
+ *   YRT_CAMERA_PERSPECTIVE, a thin lens. Q.c = o.c + (u-0.5f)*w*x.c + (v-0.5f)*h*y.c - focus*z.c
+ *     is the point of the focal plane the sample looks at (eval_camera's expression). A is the
+ *     lens diameter, as in Yocto: `aperture` >= 0, or the scene camera's own when `aperture` < 0.
+ *     With A == 0.0f the origin is e = o: eval_camera's ray bit for bit, and the call's image is
+ *     yrt_render's bit for bit. Otherwise R = A*0.5f, k = q & 63, (tx, ty) = dirs[k].xy,
+ *     t = (i & 3) | ((j & 3) << 2), r = (t ^ (q >> 6)) & 15, (c, sn) = rots[r],
+ *     lx = R*(c*tx - sn*ty), ly = R*(sn*tx + c*ty), e.c = (o.c + lx*x.c) + ly*y.c.
+ *     The ray is {e, normalize(Q - e)}. dirs and rots are yrt_ao_tables' tables: dirs[k].xy is
+ *     the Halton (2, 3) point k + 1 mapped uniformly onto the unit disk, so a pixel with
+ *     ns*ns <= 64 uses the first ns*ns points under one of 16 rotations, chosen per 4 x 4 pixel
+ *     tile, and beyond 64 samples the set repeats under another rotation. What lies at the
+ *     distance `focus` is sharp; a point at distance d blurs over A*|d - focus|/d there.
+ *   YRT_CAMERA_ORTHOGRAPHIC. e.c = o.c + (u-0.5f)*w*x.c + (v-0.5f)*h*y.c and
+ *     d = normalize({-z.x, -z.y, -z.z}): the film is the w x h rectangle at the focus distance,
+ *     so something at that distance has the size it has in the perspective view. The aperture is
+ *     ignored.
+ *   YRT_CAMERA_EQUIRECT, the 360 x 180 degree panorama. phi = (u-0.5f)*6.2831855f,
+ *     th = v*3.1415927f, st = sinf(th), ct = cosf(th), sp = sinf(phi), cp = cosf(phi), a = st*sp,
+ *     g = st*cp, d = normalize({(a*x.c - ct*y.c) - g*z.c}), e = o: the image centre looks along
+ *     -z, the top row up, the left and right edges along +z. sinf and cosf are the device's, so a
+ *     direction is reproducible on one device and within 2^-18 of the exact one per component.
+ *     Aperture and focus are ignored. Pass width = 2 * resolution for pixels square in angle.
+ * yrt_render_camera: `out` has yrt_render's window layout and out_stride (padding columns keep the
+ * caller's bytes, local rows past the image edge are zeros); a pixel is the float32 sum of its
+ * ns*ns rays' shade() colours in the order of q from +0, divided by float(ns*ns), .w = 1: the box
+ * filter of yrt_shade_rays over yrt_camera_rays' records, bit for bit. An empty window writes
+ * nothing and counts nothing. A host `out` makes the call synchronous; a device `out` (16-byte
+ * aligned) is stream-ordered, except for the waits a reflective batch makes on its level counts.
+ * Every field of `p` means what it means in yrt_render, except that YRT_ALGO_MEGAKERNEL,
+ * count_work = 1 and a band interleave other than band = 1, band_stride = 1, band_offset = 0
+ * return YRT_ERR_UNSUPPORTED. The rays are shaded in batches of whole pixels, chunk_pixels each
+ * (0: sized to the workspace), which never changes a bit. The tile-list mode and the LDS staging
+ * of the handle do not apply: a batch builds no lists and stages nothing, and
+ * yrt_scene_tile_lists / yrt_scene_lds_staging report that. yrt_last_stats reports the sums over
+ * the batches: camera_samples == window image pixels * ns*ns, and rays, shadow_rays,
+ * shadow_rays_culled and depth_truncated as yrt_shade_rays reports them for those rays;
+ * yrt_last_timings the ray generation under YRT_PHASE_PRIMARY beside the batches' level 0 and
+ * the pixels' sums under YRT_PHASE_ACCUMULATE.
+ * yrt_camera_rays: the rays alone, n = tile_w * tile_h * ns*ns records {o.xyz, d.xyz, tmin, tmax}
+ * (32 B each, yrt_shade_rays' input) in the order (window row, window column, jj, ii), into host
+ * or device memory (16-byte aligned). The window must lie inside the image, else
+ * YRT_ERR_INVALID_ARG; a band interleave is YRT_ERR_UNSUPPORTED as above; ambient, max_depth and
+ * algorithm are ignored, and no counter is touched.
+ * Both: a null handle, p, model, out or rays, a model outside 0..2, a NaN or infinite aperture
+ * or focus, chunk_pixels < 0, a bad `mem` or a bad camera index return YRT_ERR_INVALID_ARG
+ * before any device call. */
+enum { YRT_CAMERA_PERSPECTIVE = 0, YRT_CAMERA_ORTHOGRAPHIC = 1, YRT_CAMERA_EQUIRECT = 2 };
+typedef struct yrt_camera_model {
+    int   model;         /* YRT_CAMERA_* */
+    float aperture;      /* lens diameter; < 0: the scene camera's; 0: pinhole */
+    float focus;         /* <= 0: the scene camera's */
+    int   chunk_pixels;  /* pixels per shading batch; 0: sized to the workspace; never changes a bit */
+} yrt_camera_model;
+void yrt_camera_model_default(yrt_camera_model* m);      /* {YRT_CAMERA_PERSPECTIVE, -1, 0, 0} */
+int  yrt_render_camera(yrt_scene* ds, const yrt_render_params* p, const yrt_camera_model* m, float* out, int mem,
+                       void* stream);
+int  yrt_camera_rays(yrt_scene* ds, const yrt_render_params* p, const yrt_camera_model* m, float* rays, int mem,
+                     void* stream);
+/* camera `index` of a host scene, as yrt_host_scene_add_camera takes it: the frame {x, y, z, o},
+ * fovy, aspect, aperture, focus; each pointer may be NULL. What a caller needs to override the
+ * focus sensibly. A bad index is YRT_ERR_INVALID_ARG. */
+int  yrt_host_scene_camera(const yrt_host_scene* hs, int index, float frame[12], float* fovy, float* aspect,
+                           float* aperture, float* focus);
+
 #ifdef __cplusplus
 }
 #endif

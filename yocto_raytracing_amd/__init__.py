@@ -24,7 +24,7 @@ from ._native import RenderParams, Stats, YrtError, check
 
 __all__ = [
     "Scene", "DeviceScene", "load_scene", "build_bvh", "raytrace", "raytrace_adaptive", "render_aovs", "render_passes", "render_light_groups",
-    "render_mattes", "matte", "render_ao", "ao_tables", "intersect_first",
+    "render_mattes", "matte", "render_ao", "ao_tables", "raytrace_camera", "camera_rays", "intersect_first",
     "intersect_any", "shade_rays", "tonemap", "save_hdr_or_ldr", "render_params", "device_count", "YrtError",
 ]
 
@@ -161,6 +161,15 @@ class Scene:
         kind = (C.c_int * max(n.value, 1))()
         check(N.lib.yrt_host_scene_shape_kinds(self._h, kind, n.value, C.byref(n)), "yrt_host_scene_shape_kinds")
         return list(kind[:n.value])
+
+    def camera(self, index: int = 0) -> dict:
+        """camera `index` as add_camera takes it: {"frame": (12,) float32 x, y, z, o; "fovy",
+        "aspect", "aperture" (the lens diameter), "focus"}"""
+        frame = np.zeros(12, np.float32)
+        v = [C.c_float() for _ in range(4)]
+        check(N.lib.yrt_host_scene_camera(self._h, int(index), frame.ctypes.data_as(C.POINTER(C.c_float)),
+                                          *[C.byref(x) for x in v]), "yrt_host_scene_camera")
+        return dict(zip(("fovy", "aspect", "aperture", "focus"), (x.value for x in v)), frame=frame)
 
     def image_size(self, resolution: int, camera: int = 0):
         w, h = C.c_int(), C.c_int()
@@ -348,6 +357,26 @@ class DeviceScene:
         check(N.lib.yrt_render_ao(self._h, C.byref(params), C.byref(ap), C.c_void_p(out_ptr), _mem(device_memory),
                                   C.c_void_p(stream or 0)), "yrt_render_ao")
 
+    def render_camera_into(self, params: RenderParams, out_ptr: int, model: str = "perspective",
+                           aperture: Optional[float] = None, focus: Optional[float] = None, chunk_pixels: int = 0,
+                           device_memory: bool = True, stream: Optional[int] = None) -> None:
+        """Launch raytrace() under a camera model (yrt_render_camera) into a caller buffer in
+        render_into's layout: "perspective" (a thin lens of diameter `aperture`, None: the scene
+        camera's, 0: the pinhole, focused at `focus`, None: the scene camera's), "orthographic" or
+        "equirect". The camera rays are generated on the device and shaded as ray batches."""
+        cm = _camera_model(model, aperture, focus, chunk_pixels)
+        check(N.lib.yrt_render_camera(self._h, C.byref(params), C.byref(cm), C.c_void_p(out_ptr), _mem(device_memory),
+                                      C.c_void_p(stream or 0)), "yrt_render_camera")
+
+    def camera_rays_into(self, params: RenderParams, rays_ptr: int, model: str = "perspective",
+                         aperture: Optional[float] = None, focus: Optional[float] = None, device_memory: bool = True,
+                         stream: Optional[int] = None) -> None:
+        """Write the camera rays of render_camera_into's frame (yrt_camera_rays): window pixels x
+        samples^2 records of 8 float32 {o.xyz, d.xyz, tmin, tmax}, ordered (row, column, jj, ii)."""
+        cm = _camera_model(model, aperture, focus, 0)
+        check(N.lib.yrt_camera_rays(self._h, C.byref(params), C.byref(cm), C.c_void_p(rays_ptr), _mem(device_memory),
+                                    C.c_void_p(stream or 0)), "yrt_camera_rays")
+
     def last_timings(self) -> dict:
         """per-phase GPU ms of the last render with timing=True: {phase: (ms, launches)}"""
         t = N.Timings()
@@ -359,6 +388,22 @@ class DeviceScene:
         s = Stats()
         check(N.lib.yrt_last_stats(self._h, C.byref(s)), "yrt_last_stats")
         return {name: int(getattr(s, name)) for name, _ in Stats._fields_}
+
+
+def _camera_model(model: str, aperture, focus, chunk_pixels: int) -> "N.CameraModel":
+    """yrt_camera_model of a model's name; None is the scene camera's aperture or focus. An
+    unknown name raises before any native call."""
+    if model not in N.CAMERA_MODELS:
+        raise ValueError(f"unknown camera model {model!r} (one of {', '.join(N.CAMERA_MODELS)})")
+    cm = N.CameraModel()
+    N.lib.yrt_camera_model_default(C.byref(cm))
+    cm.model = N.CAMERA_MODELS[model]
+    if aperture is not None:
+        cm.aperture = float(aperture)
+    if focus is not None:
+        cm.focus = float(focus)
+    cm.chunk_pixels = int(chunk_pixels)
+    return cm
 
 
 class MultiScene:
@@ -540,6 +585,43 @@ def raytrace_adaptive(scn, amb: Sequence[float] = (0.1, 0.1, 0.1), resolution: i
     if return_stats:
         out += (dict(ds.last_stats(), refined_pixels=ds.adaptive_refined()),)
     return out if len(out) > 1 else img
+
+
+def raytrace_camera(scn, amb: Sequence[float] = (0.1, 0.1, 0.1), resolution: int = 720, samples: int = 1, *,
+                    model: str = "perspective", aperture: Optional[float] = None, focus: Optional[float] = None,
+                    width: int = 0, window=None, max_depth: int = 16, camera: int = 0, algorithm: str = "wavefront",
+                    chunk_pixels: int = 0, return_stats: bool = False):
+    """raytrace under another camera model: "perspective" is a thin lens of diameter `aperture`
+    (None: the scene camera's own, 0: the pinhole, which gives raytrace's image bit for bit)
+    focused at the distance `focus` (None: the scene camera's), "orthographic" a film of the
+    perspective view's size at the focus distance, "equirect" the 360 x 180 degree panorama
+    (pass width = 2 * resolution for pixels that are square in angle). The camera rays are
+    generated on the GPU, shaded as ray batches and box filtered there: the image equals the box
+    filter of shade_rays(camera_rays(...)) bit for bit. `chunk_pixels` (0: chosen by the library)
+    sizes the batches and never changes a bit. Returns the (H, W, 4) float32 image, with
+    `return_stats` also last_stats(). `scn` is a Scene or a DeviceScene, as for raytrace."""
+    ds = _device_scene(scn)
+    p = render_params(amb, resolution, samples, width=width, max_depth=max_depth, camera=camera, window=window,
+                      algorithm=algorithm)
+    h, w = _window_shape(ds, p, window)
+    img = np.zeros((h, w, 4), np.float32)
+    ds.render_camera_into(p, img.ctypes.data, model, aperture, focus, chunk_pixels, device_memory=False)
+    if return_stats:
+        return img, ds.last_stats()
+    return img
+
+
+def camera_rays(scn, resolution: int = 720, samples: int = 1, *, model: str = "perspective",
+                aperture: Optional[float] = None, focus: Optional[float] = None, width: int = 0, window=None,
+                camera: int = 0) -> np.ndarray:
+    """The camera rays raytrace_camera shades, (n, 8) float32 {o.xyz, d.xyz, tmin, tmax} in the
+    order (row, column, jj, ii) of the window (or the whole image): shade_rays' input."""
+    ds = _device_scene(scn)
+    p = render_params(resolution=resolution, samples=samples, width=width, camera=camera, window=window)
+    h, w = _window_shape(ds, p, window)
+    rays = np.zeros((h * w * int(samples) ** 2, 8), np.float32)
+    ds.camera_rays_into(p, rays.ctypes.data, model, aperture, focus, device_memory=False)
+    return rays
 
 
 def render_aovs(scn, resolution: int = 720, samples: int = 1, *, aovs: Sequence[str] = tuple(N.AOVS),

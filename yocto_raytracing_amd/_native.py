@@ -140,8 +140,19 @@ class AoParams(C.Structure):
     _fields_ = [("rays", C.c_int), ("distance", C.c_float), ("bias", C.c_float)]
 
 
+# yrt_render_camera / yrt_camera_rays: YRT_CAMERA_* by name; the lens diameter (< 0: the scene
+# camera's, 0: pinhole), the focus distance (<= 0: the scene camera's), the pixels per shading
+# batch (0: sized by the library)
+CAMERA_MODELS = {"perspective": 0, "orthographic": 1, "equirect": 2}
+
+
+class CameraModel(C.Structure):
+    _fields_ = [("model", C.c_int), ("aperture", C.c_float), ("focus", C.c_float), ("chunk_pixels", C.c_int)]
+
+
 _vp = C.c_void_p
 _ip =C.POINTER(C.c_int)
+_fp = C.POINTER(C.c_float)
 _sig = {
     "yrt_abi_version": (C.c_int, []),
     "yrt_status_string": (C.c_char_p, [C.c_int]),
@@ -203,6 +214,10 @@ _sig = {
     "yrt_ao_tables": (C.c_int, [C.POINTER(C.c_float), C.POINTER(C.c_float)]),
     "yrt_render_ao": (C.c_int, [_vp, C.POINTER(RenderParams), C.POINTER(AoParams), _vp, C.c_int, _vp]),
     "yrt_host_scene_shape_kinds": (C.c_int, [_vp, _ip, C.c_int, _ip]),
+    "yrt_camera_model_default": (None, [C.POINTER(CameraModel)]),
+    "yrt_render_camera": (C.c_int, [_vp, C.POINTER(RenderParams), C.POINTER(CameraModel), _vp, C.c_int, _vp]),
+    "yrt_camera_rays": (C.c_int, [_vp, C.POINTER(RenderParams), C.POINTER(CameraModel), _vp, C.c_int, _vp]),
+    "yrt_host_scene_camera": (C.c_int, [_vp, C.c_int, _fp, _fp, _fp, _fp, _fp]),
 }
 EXPORTS = tuple(_sig)
 

@@ -16,6 +16,8 @@
 #include "../../include/yrt.h"
 #include "ao_args.h"
 #include "ao_tables.h"
+#include "camera_args.h"
+#include "camera_models.h"
 #include "matte_args.h"
 #include "plane_staging.h"
 #include "yrt_render.h"
@@ -367,6 +369,21 @@ int yrt_host_image_size(const yrt_host_scene* hs, int camera, int resolution, in
         return YRT_ERR_INVALID_ARG;
     *w = (int)std::round(hs->scn.cameras[camera].aspect * resolution);
     *h = resolution;
+    return YRT_OK;
+}
+
+int yrt_host_scene_camera(const yrt_host_scene* hs, int index, float frame[12], float* fovy, float* aspect,
+                          float* aperture, float* focus) {
+    if (!hs || index < 0 || index >= (int)hs->scn.cameras.size()) return YRT_ERR_INVALID_ARG;
+    const yrt::camera& c = hs->scn.cameras[index];
+    if (frame) {
+        const yrt::vec3f v[4] = {c.frame.x, c.frame.y, c.frame.z, c.frame.o};
+        for (int k = 0; k < 4; k++) frame[3 * k] = v[k].x, frame[3 * k + 1] = v[k].y, frame[3 * k + 2] = v[k].z;
+    }
+    if (fovy) *fovy = c.fovy;
+    if (aspect) *aspect = c.aspect;
+    if (aperture) *aperture = c.aperture;
+    if (focus) *focus = c.focus;
     return YRT_OK;
 }
 
@@ -1021,6 +1038,105 @@ int yrt_render_ao(yrt_scene* s, const yrt_render_params* p, const yrt_ao_params*
         else
             stage_host_planes(list, a.out_stride > r.tw, st, "hipMalloc(ao staging)", "ao render", launch);
         return YRT_OK;
+    });
+}
+
+void yrt_camera_model_default(yrt_camera_model* m) {
+    if (!m) return;
+    m->model = YRT_CAMERA_PERSPECTIVE;
+    m->aperture = -1.0f;
+    m->focus = 0.0f;
+    m->chunk_pixels = 0;
+}
+
+static_assert(YRT_CAMERA_PERSPECTIVE == yrt::camera_perspective && YRT_CAMERA_ORTHOGRAPHIC == yrt::camera_orthographic &&
+                  YRT_CAMERA_EQUIRECT == yrt::camera_equirect,
+              "the kernel's models are the header's");
+
+namespace {
+// what yrt_render_camera and yrt_camera_rays refuse before the handle is looked at
+const char* camera_call_error(const yrt_scene* s, const yrt_render_params* p, const yrt_camera_model* m, const float* out,
+                              int mem) {
+    return !s              ? "camera: null scene handle"
+           : !p            ? "camera: null params"
+           : p->camera < 0 ? "camera: camera index out of range"
+                           : yrt::camera_args_error(m, out, mem);
+}
+
+// the call's frame: frame_args with the scene camera's focus replaced by the model's, and the
+// resolved model; refuses a band interleave
+yrt::dev_render_args camera_frame_args(const yrt_scene* s, const yrt_render_params& p, const resolved_window& r,
+                                       const yrt_camera_model& m, bool shading, yrt::camera_resolved& cm) {
+    yrt::dev_render_args a = frame_args(s, p, &r, shading);
+    yrt::camera c = s->ds->cameras[p.camera];
+    cm = yrt::camera_resolve(m, c.aperture, c.focus);
+    c.focus = cm.focus;
+    a.cam = yrt::make_dev_camera(c);
+    if (p.band != 1 || p.band_stride != 1 || p.band_offset != 0)
+        throw yrt::unsupported_error("camera models take contiguous rows: no band interleave");
+    return a;
+}
+}  // namespace
+
+int yrt_render_camera(yrt_scene* s, const yrt_render_params* p, const yrt_camera_model* m, float* out, int mem,
+                      void* stream) {
+    // (before any device call, and before the handle is looked at)
+    if (const char* bad = camera_call_error(s, p, m, out, mem)) {
+        g_last_error = bad;
+        return YRT_ERR_INVALID_ARG;
+    }
+    return guarded([&] {
+        auto r = resolve(*s->ds, *p);
+        yrt::camera_resolved cm;
+        const yrt::dev_render_args a = camera_frame_args(s, *p, r, *m, true, cm);  // (refusals before any device call)
+        if (p->algorithm == YRT_ALGO_MEGAKERNEL) throw yrt::unsupported_error("camera models run in the wavefront algorithms");
+        if (p->algorithm != YRT_ALGO_WAVEFRONT && p->algorithm != YRT_ALGO_WAVEFRONT_LANE)
+            throw std::invalid_argument("unknown algorithm");
+        if (p->count_work != 0) throw yrt::unsupported_error("camera models do not count work");
+        hipStream_t st = (hipStream_t)stream;
+        hip_check(hipSetDevice(s->ds->device), "hipSetDevice");
+        start_timer(s, *p);
+        s->last_stream = st;
+        const yrt::plane_list list = yrt::ao_plane_list(out, (size_t)a.out_stride * r.th * 16);
+        auto launch = [&](void* staging) {
+            return yrt::launch_render_camera(*s->ds, a, cm.model, cm.aperture, m->chunk_pixels, list.plane(0, staging),
+                                             s->counters, p->algorithm == YRT_ALGO_WAVEFRONT, st);
+        };
+        // (an empty window launches nothing but the counters' memset: the plane is not touched)
+        if (mem == YRT_MEM_DEVICE || r.tw <= 0 || r.th <= 0)
+            hip_check(launch(nullptr), "camera render launch");
+        else
+            stage_host_planes(list, a.out_stride > r.tw, st, "hipMalloc(camera staging)", "camera render", launch);
+        return YRT_OK;
+    });
+}
+
+int yrt_camera_rays(yrt_scene* s, const yrt_render_params* p, const yrt_camera_model* m, float* rays, int mem,
+                    void* stream) {
+    // (before any device call, and before the handle is looked at)
+    if (const char* bad = camera_call_error(s, p, m, rays, mem)) {
+        g_last_error = bad;
+        return YRT_ERR_INVALID_ARG;
+    }
+    return guarded([&] {
+        yrt_render_params q = *p;
+        q.out_stride = 0;  // (the records have no rows)
+        auto r = resolve(*s->ds, q);
+        if (r.tw <= 0 || r.th <= 0) return (int)YRT_OK;
+        if (r.y0 + r.th > r.H) throw std::invalid_argument("window taller than image");
+        if (mem == YRT_MEM_DEVICE && ((uintptr_t)rays & 15)) throw std::invalid_argument("device rays are 16-byte aligned");
+        yrt::camera_resolved cm;
+        const yrt::dev_render_args a = camera_frame_args(s, q, r, *m, false, cm);
+        hipStream_t st = (hipStream_t)stream;
+        hip_check(hipSetDevice(s->ds->device), "hipSetDevice");
+        const size_t bytes = (size_t)r.tw * r.th * q.samples * q.samples * 32;
+        void* dst = mem == YRT_MEM_DEVICE ? (void*)rays : scratch(s, bytes);
+        hip_check(yrt::launch_camera_rays(*s->ds, a, cm.model, cm.aperture, dst, st), "camera rays launch");
+        if (mem != YRT_MEM_DEVICE) {
+            hip_check(hipMemcpyAsync(rays, dst, bytes, hipMemcpyDeviceToHost, st), "hipMemcpyAsync");
+            hip_check(hipStreamSynchronize(st), "hipStreamSynchronize");
+        }
+        return (int)YRT_OK;
     });
 }
 

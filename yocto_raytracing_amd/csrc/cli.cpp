@@ -12,7 +12,9 @@
 // --mattes LIST with --matte-ranks 4|8 (ID mattes: per key the ranked ids covering each pixel and
 // their coverages, from one pass, as .npy files), --adaptive THRESHOLD with --base-samples N (the
 // image with adaptive supersampling, and the refined pixels' mask as a .npy file),
-// --ao K[,DISTANCE[,BIAS]] (the ambient occlusion plane as a .npy file).
+// --ao K[,DISTANCE[,BIAS]] (the ambient occlusion plane as a .npy file), --camera-model
+// perspective|orthographic|equirect with --aperture A and --focus F (the image under another
+// camera model: a thin lens, an orthographic film, a panorama).
 #include <algorithm>
 #include <chrono>
 #include <cstdio>
@@ -61,7 +63,13 @@ namespace {
             "  --base-samples N     samples per axis of --adaptive's base frame [1]\n"
             "  --ao K[,DIST[,BIAS]] also write OUT.ao.npy, (H, W, 4) float32 {a, a, a, coverage}: a the share of K\n"
             "                       (1 to 64) cosine-weighted rays per camera sample, from BIAS [0.01] to DIST\n"
-            "                       [unbounded], that nothing occludes, times the coverage (one GPU)\n");
+            "                       [unbounded], that nothing occludes, times the coverage (one GPU)\n"
+            "  --camera-model NAME  perspective | orthographic | equirect: render the image under this camera\n"
+            "                       model, its rays generated on the GPU (one GPU, a wavefront algorithm);\n"
+            "                       perspective is a thin lens with the scene camera's aperture and focus,\n"
+            "                       equirect the 360 x 180 degree panorama (give --width 2 * -r)\n"
+            "  --aperture A         lens diameter of the perspective model, 0 for the pinhole [the camera's]\n"
+            "  --focus F            focus distance of the perspective and orthographic models [the camera's]\n");
     exit(msg ? 1 : 0);
 }
 
@@ -113,6 +121,15 @@ yrt_ao_params parse_ao(const std::string& list) {
     return ao;
 }
 
+// --aperture's and --focus' value: a finite number >= 0, > 0 when `open`
+float parse_lens(const char* v, const char* opt, bool open) {
+    char* end = nullptr;
+    const float x = strtof(v, &end);
+    if (!*v || *end || !(x >= 0.0f) || x > 3.402823466e+38f || (open && x == 0.0f))
+        usage((std::string(opt) + (open ? " takes a finite number > 0" : " takes a finite number >= 0")).c_str());
+    return x;
+}
+
 // --light-groups' comma-separated group of each light
 std::vector<int> parse_light_groups(const std::string& list) {
     std::vector<int> groups;
@@ -162,6 +179,9 @@ int main(int argc, char** argv) {
     yrt_ao_params ao_params = {};
     float threshold = 0.0f;
     int base_samples = 1;
+    bool camera = false, aperture_given = false;  // --camera-model, --aperture or --focus: yrt_render_camera
+    yrt_camera_model camera_model;
+    yrt_camera_model_default(&camera_model);
     std::string out = "out.png", scenein;
     for (int k = 1; k < argc; k++) {
         std::string a = argv[k];
@@ -197,6 +217,15 @@ int main(int argc, char** argv) {
             adaptive = true;
         } else if (a == "--base-samples") base_samples = parse_int(val(), "--base-samples");
         else if (a == "--ao") ao_params = parse_ao(val()), ao = true;
+        else if (a == "--camera-model") {
+            std::string n = val();
+            if (n == "perspective") camera_model.model = YRT_CAMERA_PERSPECTIVE;
+            else if (n == "orthographic") camera_model.model = YRT_CAMERA_ORTHOGRAPHIC;
+            else if (n == "equirect") camera_model.model = YRT_CAMERA_EQUIRECT;
+            else usage(("unknown --camera-model " + n + ": perspective, orthographic or equirect").c_str());
+            camera = true;
+        } else if (a == "--aperture") camera_model.aperture = parse_lens(val(), "--aperture", false), camera = aperture_given = true;
+        else if (a == "--focus") camera_model.focus = parse_lens(val(), "--focus", true), camera = true;
         else if (a == "-h" || a == "--help") usage(nullptr);
         else if (!a.empty() && a[0] == '-') usage(("unknown option " + a).c_str());
         else if (scenein.empty()) scenein = a;
@@ -219,6 +248,12 @@ int main(int argc, char** argv) {
         usage("--adaptive needs a wavefront algorithm, not --algorithm megakernel");
     if (adaptive && (passes || groups)) usage("--adaptive renders the image alone: not with --passes or --light-groups");
     if (adaptive && (base_samples < 1 || base_samples > samples)) usage("--base-samples must be from 1 to -s");
+    if (camera && gpus > 1) usage("--camera-model, --aperture and --focus render on one GPU (--gpus 1)");
+    if (camera && algorithm == YRT_ALGO_MEGAKERNEL)
+        usage("--camera-model, --aperture and --focus need a wavefront algorithm, not --algorithm megakernel");
+    if (camera && (passes || groups || adaptive))
+        usage("--camera-model, --aperture and --focus render the image alone: not with --passes, --light-groups or --adaptive");
+    if (aperture_given && camera_model.model != YRT_CAMERA_PERSPECTIVE) usage("--aperture is the perspective model's lens");
     try {
         printf("loading scene %s\n", scenein.c_str());
         auto scn = yrt_cpp::load_scene(scenein);
@@ -288,6 +323,17 @@ int main(int argc, char** argv) {
             const unsigned long long n = yrt_cpp::adaptive_refined(scn);
             printf("adaptive: refined %llu of %llu pixels (%.1f %%)\n", n, (unsigned long long)refined.size(),
                    refined.empty() ? 0.0 : 100.0 * (double)n / (double)refined.size());
+        } else if (camera) {
+            // the image under the camera model, in host memory
+            yrt_render_params p = scn->params;
+            p.ambient[0] = p.ambient[1] = p.ambient[2] = amb;
+            p.resolution = resolution;
+            p.samples = samples;
+            int w = 0, h = 0;
+            yrt_cpp::check(yrt_image_size(scn->on_device(), &p, &w, &h), "raytrace");
+            hdr = yrt_cpp::image4f(w, h);
+            yrt_cpp::check(yrt_render_camera(scn->on_device(), &p, &camera_model, &hdr.pixels[0].x, YRT_MEM_HOST, nullptr),
+                           "render_camera");
         } else
             hdr = yrt_cpp::raytrace(scn, {amb, amb, amb}, resolution, samples);
         auto t1 = std::chrono::steady_clock::now();

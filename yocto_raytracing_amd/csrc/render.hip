@@ -387,3 +387,5 @@ hipError_t launch_tonemap(const float* rgba, int n, unsigned char* out, const to
 #include "adaptive.hip"
 // ambient occlusion (k_ao, launch_ao), on the AOV pass's tile geometry
 #include "ao.hip"
+// camera models (k_camera_rays, k_camera_resolve, launch_render_camera), on adaptive.hip's batches
+#include "camera.hip"

@@ -239,4 +239,21 @@ hipError_t launch_render_adaptive(device_scene& ds, const dev_render_args& args,
                                   int chunk_pixels, void* out_rgba, unsigned char* refined,
                                   unsigned long long* counters, bool packet, hipStream_t stream);
 
+// camera models (camera.hip, yrt_render_camera / yrt_camera_rays): `model` is a camera_model of
+// camera_models.h and `aperture` the resolved lens diameter (camera_args.h); args is the call's
+// frame with the call's focus in args.cam (contiguous rows: band 1, stride 1, offset 0).
+// launch_render_camera writes the window's image: k_camera_rays generates a chunk of whole
+// pixels' rays, launch_shade_rays_wavefront shades them, k_camera_resolve sums each pixel's
+// colours into out_rgba, chunk_pixels pixels a batch (0: as many as keep a chunk within
+// adaptive_chunk_rays rays). The chunks' rays and colours live in ds.adaptive_rays and the saved
+// counter lines in ds.adaptive_frame. The counters are the batches' sums; timings are added per
+// phase; the handle reports no lists and no staging afterwards.
+hipError_t launch_render_camera(device_scene& ds, const dev_render_args& args, int model, float aperture,
+                                int chunk_pixels, void* out_rgba, unsigned long long* counters, bool packet,
+                                hipStream_t stream);
+// k_camera_rays alone over the whole window (which lies inside the image), tile_w * tile_h *
+// samples^2 records of 32 bytes into `rays` (device memory); touches no counter
+hipError_t launch_camera_rays(device_scene& ds, const dev_render_args& args, int model, float aperture, void* rays,
+                              hipStream_t stream);
+
 }  // namespace yrt
