@@ -597,6 +597,62 @@ int  yrt_camera_rays(yrt_scene* ds, const yrt_render_params* p, const yrt_camera
 int  yrt_host_scene_camera(const yrt_host_scene* hs, int index, float frame[12], float* fovy, float* aspect,
                            float* aperture, float* focus);
 
+/* ---- soft shadows: area lights as K any-hit rays per light ----
+ * shade() casts one shadow ray per (hit, light): every light is a point and every shadow edge a
+ * step. These two calls give light li -- the li-th light in scene order, as in
+ * yrt_host_scene_lights -- a radius R_li >= 0: `radius` for all, or light_radius[li]. A light is
+ * then a disk of that radius about its point, facing the shading point, and a hit casts K = rays
+ * shadow rays at it (1..64; 0 means 16). All arithmetic is float32, left to right as written,
+ * with no contraction; bits(x) is the float's 32-bit pattern; dirs and rots are yrt_ao_tables'
+ * tables. For a sample that hit, at any level, with hit point p, and light li:
+ *   1. tp, l, r are the hard shadow ray's: tp = transform_point(lf, lp0 - p), r = |tp|, l = tp / r.
+ *   2. R_li == 0.0f: the one ray {p, l, 0.01f, r - 0.01f}, the hard shadow ray bit for bit;
+ *      open = K if it is unoccluded, else 0. No basis, no offset (a -0 of tp stays what it is).
+ *   3. Otherwise u = bits(p.x + 0.0f) ^ bits(p.y + 0.0f) ^ bits(p.z + 0.0f); u ^= u >> 16;
+ *      u ^= u >> 8; u ^= u >> 4; rot = (u ^ li) & 15; (c, sn) = rots[rot]. The rotation depends on
+ *      the hit point and the light alone -- not on a pixel, a batch index or a compaction slot --
+ *      so the rays have the same bits under any schedule, chunk size and level.
+ *   4. The basis about l (Duff et al.): sg = l.z >= 0 ? 1 : -1, a = -1/(sg + l.z), b = l.x*l.y*a,
+ *      b1 = {1 + sg*l.x*l.x*a, sg*b, -sg*l.x}, b2 = {b, sg + l.y*l.y*a, -l.y}.
+ *   5. For k = 0..K-1: (tx, ty) = dirs[k].xy, x = c*tx - sn*ty, y = sn*tx + c*ty,
+ *      tq = tp + (b1*x + b2*y) * R_li, rq = |tq|, lq = tq / rq, the ray {p, lq, 0.01f, rq - 0.01f},
+ *      answered by intersect_any. open is the number of unoccluded rays.
+ *   6. open == 0: the light is skipped, as an occluded light is in shade(). Otherwise
+ *      f = float(open) / float(K) and c = c + (ld + ls) * f, ld and ls being shade()'s terms of the
+ *      centre l, r, unchanged: open == K gives f == 1.0f and shade()'s bits. A light whose term is
+ *      proven +-0 (the zero-term cull of yrt_render) may be answered without a walk, as open = 0.
+ *   7. Everything else is shade() as yrt_shade_rays states it: the view vector from the ray's own
+ *      origin, the mirror recursion, max_depth, the fold.
+ * So with every radius 0 the result is yrt_shade_rays' / yrt_render's bit for bit whatever K is, a
+ * pixel's value depends on its own rays alone, and the result has the same bits on every run.
+ * The approximation: the light's term is taken at its centre, the disk faces the
+ * shading point, and no light is sampled by solid angle.
+ * yrt_shade_rays_soft is yrt_shade_rays with these shadow rays: the same records, layout, memory
+ * kinds, stream order and n == 0. yrt_render_soft_shadows is yrt_render_camera with them: `m` is
+ * the camera model (NULL: the pinhole, {YRT_CAMERA_PERSPECTIVE, 0, 0, 0}), so soft shadows and a
+ * thin lens combine; window, out_stride, host and device memory, stream order, empty windows,
+ * chunk_pixels and the refused band interleave are yrt_render_camera's. Both run in the wavefront
+ * algorithms only: YRT_ALGO_MEGAKERNEL and count_work = 1 return YRT_ERR_UNSUPPORTED. The
+ * tile-list mode and the LDS staging of the handle do not apply and are reported unused.
+ * yrt_last_stats: a (hit sample, light) pair counts K shadow rays when R_li > 0 and 1 when
+ * R_li == 0, a pair answered by the zero-term cull the same number in shadow_rays_culled; rays is
+ * the closest-hit rays plus shadow_rays; camera_samples as after yrt_render_camera.
+ * A null handle, p, soft params, rays or out, K outside 0..64, a negative, NaN or infinite
+ * radius, nlights other than the scene's light count when light_radius is given, a bad `mem`,
+ * camera or model return YRT_ERR_INVALID_ARG before any device call. */
+#define YRT_SOFT_SHADOW_RAYS_MAX 64
+typedef struct yrt_soft_shadow_params {
+    int rays;                   /* K: 0 -> 16; 1..64 */
+    float radius;               /* every light's radius when light_radius is NULL; >= 0, finite */
+    const float* light_radius;  /* host memory, nlights entries, or NULL */
+    int nlights;                /* the scene's light count when light_radius is given */
+} yrt_soft_shadow_params;
+void yrt_soft_shadow_params_default(yrt_soft_shadow_params* sp);   /* {16, 0, NULL, 0} */
+int  yrt_shade_rays_soft(yrt_scene* ds, const yrt_render_params* p, const yrt_soft_shadow_params* sp,
+                         const float* rays, int n, float* out_rgba, int mem, void* stream);
+int  yrt_render_soft_shadows(yrt_scene* ds, const yrt_render_params* p, const yrt_camera_model* m /* NULL: pinhole */,
+                             const yrt_soft_shadow_params* sp, float* out, int mem, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

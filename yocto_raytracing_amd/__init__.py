@@ -24,7 +24,8 @@ from ._native import RenderParams, Stats, YrtError, check
 
 __all__ = [
     "Scene", "DeviceScene", "load_scene", "build_bvh", "raytrace", "raytrace_adaptive", "render_aovs", "render_passes", "render_light_groups",
-    "render_mattes", "matte", "render_ao", "ao_tables", "raytrace_camera", "camera_rays", "intersect_first",
+    "render_mattes", "matte", "render_ao", "ao_tables", "raytrace_camera", "camera_rays", "raytrace_soft",
+    "shade_rays_soft", "intersect_first",
     "intersect_any", "shade_rays", "tonemap", "save_hdr_or_ldr", "render_params", "device_count", "YrtError",
 ]
 
@@ -377,6 +378,28 @@ class DeviceScene:
         check(N.lib.yrt_camera_rays(self._h, C.byref(params), C.byref(cm), C.c_void_p(rays_ptr), _mem(device_memory),
                                     C.c_void_p(stream or 0)), "yrt_camera_rays")
 
+    def render_soft_shadows_into(self, params: RenderParams, out_ptr: int, radius: float = 0.0, light_radii=None,
+                                 shadow_rays: int = 16, model: str = "perspective", aperture: Optional[float] = 0.0,
+                                 focus: Optional[float] = None, chunk_pixels: int = 0, device_memory: bool = True,
+                                 stream: Optional[int] = None) -> None:
+        """Launch raytrace() with soft shadows (yrt_render_soft_shadows) into a caller buffer in
+        render_into's layout: every light is a disk of `radius` (or light_radii[li], Scene.lights()
+        order) facing the shading point, sampled by `shadow_rays` any-hit rays per hit and light;
+        radius 0 is the point light. The camera is render_camera_into's (the pinhole by default)."""
+        cm = _camera_model(model, aperture, focus, chunk_pixels)
+        sp, _keep = _soft_params(radius, light_radii, shadow_rays)
+        check(N.lib.yrt_render_soft_shadows(self._h, C.byref(params), C.byref(cm), C.byref(sp), C.c_void_p(out_ptr),
+                                            _mem(device_memory), C.c_void_p(stream or 0)), "yrt_render_soft_shadows")
+
+    def shade_rays_soft_into(self, params: RenderParams, rays_ptr: int, n: int, out_ptr: int, radius: float = 0.0,
+                             light_radii=None, shadow_rays: int = 16, device_memory: bool = True,
+                             stream: Optional[int] = None) -> None:
+        """shade_rays_into with render_soft_shadows_into's lights (yrt_shade_rays_soft)."""
+        sp, _keep = _soft_params(radius, light_radii, shadow_rays)
+        check(N.lib.yrt_shade_rays_soft(self._h, C.byref(params), C.byref(sp), C.c_void_p(rays_ptr), int(n),
+                                        C.c_void_p(out_ptr), _mem(device_memory), C.c_void_p(stream or 0)),
+              "yrt_shade_rays_soft")
+
     def last_timings(self) -> dict:
         """per-phase GPU ms of the last render with timing=True: {phase: (ms, launches)}"""
         t = N.Timings()
@@ -404,6 +427,19 @@ def _camera_model(model: str, aperture, focus, chunk_pixels: int) -> "N.CameraMo
         cm.focus = float(focus)
     cm.chunk_pixels = int(chunk_pixels)
     return cm
+
+
+def _soft_params(radius: float, light_radii, shadow_rays: int) -> tuple:
+    """(yrt_soft_shadow_params, the array its light_radius points into)"""
+    sp = N.SoftShadowParams()
+    N.lib.yrt_soft_shadow_params_default(C.byref(sp))
+    sp.rays, sp.radius = int(shadow_rays), float(radius)
+    radii = None
+    if light_radii is not None:
+        radii = np.ascontiguousarray(light_radii, dtype=np.float32).reshape(-1)
+        keep = radii if radii.size else np.zeros(1, np.float32)  # (no lights: a pointer that is not null)
+        sp.light_radius, sp.nlights, radii = keep.ctypes.data_as(C.POINTER(C.c_float)), int(radii.size), keep
+    return sp, radii
 
 
 class MultiScene:
@@ -606,6 +642,39 @@ def raytrace_camera(scn, amb: Sequence[float] = (0.1, 0.1, 0.1), resolution: int
     h, w = _window_shape(ds, p, window)
     img = np.zeros((h, w, 4), np.float32)
     ds.render_camera_into(p, img.ctypes.data, model, aperture, focus, chunk_pixels, device_memory=False)
+    if return_stats:
+        return img, ds.last_stats()
+    return img
+
+
+def raytrace_soft(scn, amb: Sequence[float] = (0.1, 0.1, 0.1), resolution: int = 720, samples: int = 1, *,
+                  radius: float = 0.0, light_radii=None, shadow_rays: int = 16, model: str = "perspective",
+                  aperture: Optional[float] = 0.0, focus: Optional[float] = None, width: int = 0, window=None,
+                  max_depth: int = 16, camera: int = 0, algorithm: str = "wavefront", chunk_pixels: int = 0,
+                  device_memory: bool = False, return_stats: bool = False):
+    """raytrace with soft shadows: every light is a disk of `radius` (or light_radii[li], in
+    Scene.lights() order) that faces the shading point, and every hit, at every mirror level,
+    casts `shadow_rays` (1..64) any-hit rays per light at it; a light's term is scaled by the
+    share that arrives. Radius 0 is the point light: with every radius 0 the image is raytrace's
+    bit for bit. The camera is raytrace_camera's (by default the pinhole, aperture 0), so soft
+    shadows and a thin lens combine. `device_memory` renders into device memory (a torch tensor)
+    and copies the plane back. Returns the (H, W, 4) float32 image, with `return_stats` also
+    last_stats()."""
+    ds = _device_scene(scn)
+    p = render_params(amb, resolution, samples, width=width, max_depth=max_depth, camera=camera, window=window,
+                      algorithm=algorithm)
+    h, w = _window_shape(ds, p, window)
+    args = (radius, light_radii, shadow_rays, model, aperture, focus, chunk_pixels)
+    if device_memory:
+        import torch
+
+        dev = torch.zeros((h, w, 4), dtype=torch.float32, device="cuda")
+        ds.render_soft_shadows_into(p, dev.data_ptr(), *args, device_memory=True,
+                                    stream=torch.cuda.current_stream().cuda_stream)
+        img = dev.cpu().numpy()
+    else:
+        img = np.zeros((h, w, 4), np.float32)
+        ds.render_soft_shadows_into(p, img.ctypes.data, *args, device_memory=False)
     if return_stats:
         return img, ds.last_stats()
     return img
@@ -823,6 +892,21 @@ def shade_rays(scn, rays, amb: Sequence[float] = (0.1, 0.1, 0.1), *, max_depth: 
     p = render_params(amb, max_depth=max_depth, algorithm=algorithm)
     out = np.zeros((r.shape[0], 4), np.float32)
     ds.shade_rays_into(p, r.ctypes.data, r.shape[0], out.ctypes.data, device_memory=False)
+    if return_stats:
+        return out, ds.last_stats()
+    return out
+
+
+def shade_rays_soft(scn, rays, amb: Sequence[float] = (0.1, 0.1, 0.1), *, radius: float = 0.0, light_radii=None,
+                    shadow_rays: int = 16, max_depth: int = 16, algorithm: str = "wavefront",
+                    return_stats: bool = False):
+    """shade_rays with raytrace_soft's lights: (n, 4) float32 {c.xyz, 1} per caller ray."""
+    r = _rays_array(rays)
+    ds = _device_scene(scn)
+    p = render_params(amb, max_depth=max_depth, algorithm=algorithm)
+    out = np.zeros((r.shape[0], 4), np.float32)
+    ds.shade_rays_soft_into(p, r.ctypes.data, r.shape[0], out.ctypes.data, radius, light_radii, shadow_rays,
+                            device_memory=False)
     if return_stats:
         return out, ds.last_stats()
     return out

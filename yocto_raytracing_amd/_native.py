@@ -150,6 +150,15 @@ class CameraModel(C.Structure):
     _fields_ = [("model", C.c_int), ("aperture", C.c_float), ("focus", C.c_float), ("chunk_pixels", C.c_int)]
 
 
+# yrt_shade_rays_soft / yrt_render_soft_shadows: K shadow rays per light (0: 16), one radius for
+# every light or light_radius[nlights] (host memory)
+YRT_SOFT_SHADOW_RAYS_MAX = 64
+
+
+class SoftShadowParams(C.Structure):
+    _fields_ = [("rays", C.c_int), ("radius", C.c_float), ("light_radius", C.POINTER(C.c_float)), ("nlights", C.c_int)]
+
+
 _vp = C.c_void_p
 _ip =C.POINTER(C.c_int)
 _fp = C.POINTER(C.c_float)
@@ -218,6 +227,11 @@ _sig = {
     "yrt_render_camera": (C.c_int, [_vp, C.POINTER(RenderParams), C.POINTER(CameraModel), _vp, C.c_int, _vp]),
     "yrt_camera_rays": (C.c_int, [_vp, C.POINTER(RenderParams), C.POINTER(CameraModel), _vp, C.c_int, _vp]),
     "yrt_host_scene_camera": (C.c_int, [_vp, C.c_int, _fp, _fp, _fp, _fp, _fp]),
+    "yrt_soft_shadow_params_default": (None, [C.POINTER(SoftShadowParams)]),
+    "yrt_shade_rays_soft": (C.c_int, [_vp, C.POINTER(RenderParams), C.POINTER(SoftShadowParams), _vp, C.c_int, _vp,
+                                      C.c_int, _vp]),
+    "yrt_render_soft_shadows": (C.c_int, [_vp, C.POINTER(RenderParams), C.POINTER(CameraModel),
+                                          C.POINTER(SoftShadowParams), _vp, C.c_int, _vp]),
 }
 EXPORTS = tuple(_sig)
 

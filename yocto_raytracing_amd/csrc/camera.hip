@@ -84,11 +84,11 @@ void launch_camera_rays_chunk(const dev_render_args& args, int model, float aper
 // the most whole pixels whose rays one launch counts in an int (adaptive.hip's cap)
 long long camera_pixels_cap(int spp) { return std::max<long long>(1, (1ll << 30) / spp); }
 
-}  // namespace
-
-hipError_t launch_render_camera(device_scene& ds, const dev_render_args& args, int model, float aperture,
-                                int chunk_pixels, void* out_rgba, unsigned long long* counters, bool packet,
-                                hipStream_t stream) {
+// launch_render_camera and launch_render_soft_shadows: the window's image in chunks of whole
+// pixels, each shaded as a ray batch (soft: as a soft one)
+hipError_t render_camera_batches(device_scene& ds, const dev_render_args& args, int model, float aperture,
+                                 int chunk_pixels, const soft_shadow_args* soft, void* out_rgba,
+                                 unsigned long long* counters, bool packet, hipStream_t stream) {
     const size_t counter_bytes = (size_t)cnt_slots * cnt_count * sizeof(unsigned long long);
     if (args.tile_w <= 0 || args.tile_h <= 0)  // an empty window: nothing written, nothing counted
         return hipMemsetAsync(counters, 0, counter_bytes, stream);
@@ -133,7 +133,8 @@ hipError_t launch_render_camera(device_scene& ds, const dev_render_args& args, i
         // call's counts so far are saved before it and added back after it
         if (k0 > 0) e = hipMemcpyAsync(saved, counters, counter_bytes, hipMemcpyDeviceToDevice, stream);
         if (e == hipSuccess)
-            e = launch_shade_rays_wavefront(ds, args, (const float*)rays, npix * spp, colours, counters, packet, stream);
+            e = launch_shade_rays_wavefront(ds, args, (const float*)rays, npix * spp, colours, counters, packet, stream,
+                                            soft);
         if (e != hipSuccess) break;
         t = T.begin(phase_accumulate, stream);
         if (k0 > 0)
@@ -145,6 +146,20 @@ hipError_t launch_render_camera(device_scene& ds, const dev_render_args& args, i
         e = hipGetLastError();
     }
     return e;
+}
+
+}  // namespace
+
+hipError_t launch_render_camera(device_scene& ds, const dev_render_args& args, int model, float aperture,
+                                int chunk_pixels, void* out_rgba, unsigned long long* counters, bool packet,
+                                hipStream_t stream) {
+    return render_camera_batches(ds, args, model, aperture, chunk_pixels, nullptr, out_rgba, counters, packet, stream);
+}
+
+hipError_t launch_render_soft_shadows(device_scene& ds, const dev_render_args& args, int model, float aperture,
+                                      int chunk_pixels, const soft_shadow_args& soft, void* out_rgba,
+                                      unsigned long long* counters, bool packet, hipStream_t stream) {
+    return render_camera_batches(ds, args, model, aperture, chunk_pixels, &soft, out_rgba, counters, packet, stream);
 }
 
 hipError_t launch_camera_rays(device_scene& ds, const dev_render_args& args, int model, float aperture, void* rays,

@@ -20,6 +20,7 @@
 #include "camera_models.h"
 #include "matte_args.h"
 #include "plane_staging.h"
+#include "soft_shadow_args.h"
 #include "yrt_render.h"
 
 struct yrt_host_scene {
@@ -877,27 +878,33 @@ int yrt_trace_any(yrt_scene* s, const float* rays, int n, unsigned char* hit, in
     return trace_impl(s, rays, n, 1, hit, nullptr, nullptr, nullptr, nullptr, mem, stream);
 }
 
-int yrt_shade_rays(yrt_scene* s, const yrt_render_params* p, const float* rays, int n, float* out, int mem,
-                   void* stream) {
+// yrt_shade_rays and, with soft parameters, yrt_shade_rays_soft; a refusal's message starts with
+// the name of the entry point that was called
+static int shade_rays_impl(yrt_scene* s, const yrt_render_params* p, const yrt_soft_shadow_params* sp, const float* rays,
+                           int n, float* out, int mem, void* stream) {
+    const char* const entry = sp ? "yrt_shade_rays_soft" : "yrt_shade_rays";
     // (before any device call, and before the handle is looked at)
-    const char* bad = n < 0                                      ? "yrt_shade_rays: rays: n < 0"
-                      : mem != YRT_MEM_HOST && mem != YRT_MEM_DEVICE ? "yrt_shade_rays: rays: mem is not YRT_MEM_*"
-                      : n > 0 && !s                              ? "yrt_shade_rays: rays: null scene handle"
-                      : n > 0 && !p                              ? "yrt_shade_rays: rays: null params"
-                      : n > 0 && !rays                           ? "yrt_shade_rays: rays: null rays"
-                      : n > 0 && !out                            ? "yrt_shade_rays: rays: null out"
+    const char* bad = n < 0                                      ? ": rays: n < 0"
+                      : mem != YRT_MEM_HOST && mem != YRT_MEM_DEVICE ? ": rays: mem is not YRT_MEM_*"
+                      : n > 0 && !s                              ? ": rays: null scene handle"
+                      : n > 0 && !p                              ? ": rays: null params"
+                      : n > 0 && !rays                           ? ": rays: null rays"
+                      : n > 0 && !out                            ? ": rays: null out"
                                                                  : nullptr;
     if (!bad && n > 0) {
         const char *r0 = (const char*)rays, *o0 = (const char*)out;
-        if (r0 < o0 + (size_t)n * 16 && o0 < r0 + (size_t)n * 32) bad = "yrt_shade_rays: out overlaps rays";
-        if (mem == YRT_MEM_DEVICE && ((uintptr_t)out & 15)) bad = "yrt_shade_rays: rays: a device out is 16-byte aligned";
+        if (r0 < o0 + (size_t)n * 16 && o0 < r0 + (size_t)n * 32) bad = ": out overlaps rays";
+        if (mem == YRT_MEM_DEVICE && ((uintptr_t)out & 15)) bad = ": rays: a device out is 16-byte aligned";
     }
     if (bad) {
-        g_last_error = bad;
+        g_last_error = std::string(entry) + bad;
         return YRT_ERR_INVALID_ARG;
     }
     if (!s) return YRT_OK;  // (n == 0 without a handle: nothing to do)
     return guarded([&] {
+        if (sp) {
+            if (const char* lights = yrt::soft_shadow_lights_error(*sp, s->ds->nlights)) throw std::invalid_argument(lights);
+        }
         hipStream_t st = (hipStream_t)stream;
         hip_check(hipSetDevice(s->ds->device), "hipSetDevice");
         if (n == 0) {  // nothing is written; the counters read zero
@@ -910,6 +917,8 @@ int yrt_shade_rays(yrt_scene* s, const yrt_render_params* p, const float* rays, 
             p->algorithm != YRT_ALGO_WAVEFRONT_LANE)
             throw std::invalid_argument("unknown algorithm");
         if (p->count_work != 0) throw yrt::unsupported_error("ray batches do not count work");
+        if (sp && p->algorithm == YRT_ALGO_MEGAKERNEL)
+            throw yrt::unsupported_error("soft shadows run in the wavefront algorithms");
         yrt::dev_render_args a = frame_args(s, *p, nullptr, true);
         a.samples = 1;
         if (p->algorithm == YRT_ALGO_MEGAKERNEL && s->ds->reflective && a.max_depth > yrt::megakernel_max_depth)
@@ -930,8 +939,13 @@ int yrt_shade_rays(yrt_scene* s, const yrt_render_params* p, const float* rays, 
             zero_counters(s, st);
             hip_check(yrt::launch_shade_rays(*s->ds, a, d_rays, n, d_out, s->counters, st), "shade_rays launch");
         } else {
+            yrt::soft_shadow_args soft = {};
+            if (sp) {
+                hip_check(yrt::upload_soft_shadow_radii(*s->ds, sp->light_radius, sp->radius, st), "soft shadow radii");
+                soft = {yrt::soft_shadow_rays_of(*sp), s->ds->soft_radius};
+            }
             hip_check(yrt::launch_shade_rays_wavefront(*s->ds, a, d_rays, n, d_out, s->counters,
-                                                       p->algorithm == YRT_ALGO_WAVEFRONT, st),
+                                                       p->algorithm == YRT_ALGO_WAVEFRONT, st, sp ? &soft : nullptr),
                       "wavefront shade_rays launch");
         }
         if (mem != YRT_MEM_DEVICE) {
@@ -940,6 +954,33 @@ int yrt_shade_rays(yrt_scene* s, const yrt_render_params* p, const float* rays, 
         }
         return YRT_OK;
     });
+}
+
+int yrt_shade_rays(yrt_scene* s, const yrt_render_params* p, const float* rays, int n, float* out, int mem,
+                   void* stream) {
+    return shade_rays_impl(s, p, nullptr, rays, n, out, mem, stream);
+}
+
+void yrt_soft_shadow_params_default(yrt_soft_shadow_params* sp) {
+    if (!sp) return;
+    sp->rays = yrt::soft_shadow_rays_default;
+    sp->radius = 0.0f;
+    sp->light_radius = nullptr;
+    sp->nlights = 0;
+}
+
+static_assert(YRT_SOFT_SHADOW_RAYS_MAX == yrt::soft_shadow_rays_max && YRT_SOFT_SHADOW_RAYS_MAX == yrt::ao_dir_count,
+              "a ray per entry of the table");
+
+int yrt_shade_rays_soft(yrt_scene* s, const yrt_render_params* p, const yrt_soft_shadow_params* sp, const float* rays,
+                        int n, float* out, int mem, void* stream) {
+    // (before any device call, and before the handle is looked at; with n == 0 too)
+    const char* bad = !s ? "soft shadows: null scene handle" : !p ? "soft shadows: null params" : yrt::soft_shadow_params_error(sp);
+    if (bad) {
+        g_last_error = std::string(bad) + " (yrt_shade_rays_soft)";
+        return YRT_ERR_INVALID_ARG;
+    }
+    return shade_rays_impl(s, p, sp, rays, n, out, mem, stream);
 }
 
 int yrt_render_adaptive(yrt_scene* s, const yrt_render_params* p, const yrt_adaptive_params* ap, float* out,
@@ -1078,14 +1119,18 @@ yrt::dev_render_args camera_frame_args(const yrt_scene* s, const yrt_render_para
 }
 }  // namespace
 
-int yrt_render_camera(yrt_scene* s, const yrt_render_params* p, const yrt_camera_model* m, float* out, int mem,
-                      void* stream) {
+// yrt_render_camera and, with soft parameters, yrt_render_soft_shadows
+static int render_camera_impl(yrt_scene* s, const yrt_render_params* p, const yrt_camera_model* m,
+                              const yrt_soft_shadow_params* sp, float* out, int mem, void* stream) {
     // (before any device call, and before the handle is looked at)
     if (const char* bad = camera_call_error(s, p, m, out, mem)) {
         g_last_error = bad;
         return YRT_ERR_INVALID_ARG;
     }
     return guarded([&] {
+        if (sp) {
+            if (const char* lights = yrt::soft_shadow_lights_error(*sp, s->ds->nlights)) throw std::invalid_argument(lights);
+        }
         auto r = resolve(*s->ds, *p);
         yrt::camera_resolved cm;
         const yrt::dev_render_args a = camera_frame_args(s, *p, r, *m, true, cm);  // (refusals before any device call)
@@ -1099,8 +1144,15 @@ int yrt_render_camera(yrt_scene* s, const yrt_render_params* p, const yrt_camera
         s->last_stream = st;
         const yrt::plane_list list = yrt::ao_plane_list(out, (size_t)a.out_stride * r.th * 16);
         auto launch = [&](void* staging) {
-            return yrt::launch_render_camera(*s->ds, a, cm.model, cm.aperture, m->chunk_pixels, list.plane(0, staging),
-                                             s->counters, p->algorithm == YRT_ALGO_WAVEFRONT, st);
+            if (!sp)
+                return yrt::launch_render_camera(*s->ds, a, cm.model, cm.aperture, m->chunk_pixels,
+                                                 list.plane(0, staging), s->counters, p->algorithm == YRT_ALGO_WAVEFRONT, st);
+            if (hipError_t e = yrt::upload_soft_shadow_radii(*s->ds, sp->light_radius, sp->radius, st); e != hipSuccess)
+                return e;
+            const yrt::soft_shadow_args soft = {yrt::soft_shadow_rays_of(*sp), s->ds->soft_radius};
+            return yrt::launch_render_soft_shadows(*s->ds, a, cm.model, cm.aperture, m->chunk_pixels, soft,
+                                                   list.plane(0, staging), s->counters,
+                                                   p->algorithm == YRT_ALGO_WAVEFRONT, st);
         };
         // (an empty window launches nothing but the counters' memset: the plane is not touched)
         if (mem == YRT_MEM_DEVICE || r.tw <= 0 || r.th <= 0)
@@ -1109,6 +1161,22 @@ int yrt_render_camera(yrt_scene* s, const yrt_render_params* p, const yrt_camera
             stage_host_planes(list, a.out_stride > r.tw, st, "hipMalloc(camera staging)", "camera render", launch);
         return YRT_OK;
     });
+}
+
+int yrt_render_camera(yrt_scene* s, const yrt_render_params* p, const yrt_camera_model* m, float* out, int mem,
+                      void* stream) {
+    return render_camera_impl(s, p, m, nullptr, out, mem, stream);
+}
+
+int yrt_render_soft_shadows(yrt_scene* s, const yrt_render_params* p, const yrt_camera_model* m,
+                            const yrt_soft_shadow_params* sp, float* out, int mem, void* stream) {
+    // (before any device call, and before the handle is looked at)
+    if (const char* bad = yrt::soft_shadow_params_error(sp)) {
+        g_last_error = std::string(bad) + " (yrt_render_soft_shadows)";
+        return YRT_ERR_INVALID_ARG;
+    }
+    const yrt_camera_model pinhole = {YRT_CAMERA_PERSPECTIVE, 0.0f, 0.0f, 0};
+    return render_camera_impl(s, p, m ? m : &pinhole, sp, out, mem, stream);
 }
 
 int yrt_camera_rays(yrt_scene* s, const yrt_render_params* p, const yrt_camera_model* m, float* rays, int mem,

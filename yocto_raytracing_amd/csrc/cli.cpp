@@ -14,7 +14,8 @@
 // image with adaptive supersampling, and the refined pixels' mask as a .npy file),
 // --ao K[,DISTANCE[,BIAS]] (the ambient occlusion plane as a .npy file), --camera-model
 // perspective|orthographic|equirect with --aperture A and --focus F (the image under another
-// camera model: a thin lens, an orthographic film, a panorama).
+// camera model: a thin lens, an orthographic film, a panorama), --soft-shadows R[,K] (the image
+// with every light a disk of radius R, K shadow rays per light).
 #include <algorithm>
 #include <chrono>
 #include <cstdio>
@@ -69,7 +70,11 @@ namespace {
             "                       perspective is a thin lens with the scene camera's aperture and focus,\n"
             "                       equirect the 360 x 180 degree panorama (give --width 2 * -r)\n"
             "  --aperture A         lens diameter of the perspective model, 0 for the pinhole [the camera's]\n"
-            "  --focus F            focus distance of the perspective and orthographic models [the camera's]\n");
+            "  --focus F            focus distance of the perspective and orthographic models [the camera's]\n"
+            "  --soft-shadows R[,K] render the image with soft shadows: every light a disk of radius R that faces\n"
+            "                       the shaded point, K (1 to 64) [16] shadow rays per light; R = 0 is the image\n"
+            "                       itself; combines with --camera-model, --aperture and --focus (one GPU, a\n"
+            "                       wavefront algorithm)\n");
     exit(msg ? 1 : 0);
 }
 
@@ -119,6 +124,26 @@ yrt_ao_params parse_ao(const std::string& list) {
     }
     if (ao.rays < 1 || ao.rays > YRT_AO_RAYS_MAX) usage("--ao: K must be from 1 to 64");
     return ao;
+}
+
+// --soft-shadows' R[,K] over the defaults of yrt_soft_shadow_params_default
+yrt_soft_shadow_params parse_soft(const std::string& list) {
+    yrt_soft_shadow_params sp;
+    yrt_soft_shadow_params_default(&sp);
+    int field = 0;
+    for (size_t at = 0; at <= list.size(); field++) {
+        size_t end = list.find(',', at);
+        if (end == std::string::npos) end = list.size();
+        const std::string item = list.substr(at, end - at);
+        char* stop = nullptr;
+        if (field == 0) sp.radius = strtof(item.c_str(), &stop);
+        else if (field == 1) sp.rays = (int)strtol(item.c_str(), &stop, 10);
+        if (field > 1 || item.empty() || *stop) usage("--soft-shadows takes R[,K]");
+        at = end + 1;
+    }
+    if (!(sp.radius >= 0.0f) || sp.radius > 3.402823466e+38f) usage("--soft-shadows: R must be a finite number >= 0");
+    if (sp.rays < 1 || sp.rays > YRT_SOFT_SHADOW_RAYS_MAX) usage("--soft-shadows: K must be from 1 to 64");
+    return sp;
 }
 
 // --aperture's and --focus' value: a finite number >= 0, > 0 when `open`
@@ -182,6 +207,8 @@ int main(int argc, char** argv) {
     bool camera = false, aperture_given = false;  // --camera-model, --aperture or --focus: yrt_render_camera
     yrt_camera_model camera_model;
     yrt_camera_model_default(&camera_model);
+    bool soft = false;  // --soft-shadows: yrt_render_soft_shadows
+    yrt_soft_shadow_params soft_params = {};
     std::string out = "out.png", scenein;
     for (int k = 1; k < argc; k++) {
         std::string a = argv[k];
@@ -226,6 +253,7 @@ int main(int argc, char** argv) {
             camera = true;
         } else if (a == "--aperture") camera_model.aperture = parse_lens(val(), "--aperture", false), camera = aperture_given = true;
         else if (a == "--focus") camera_model.focus = parse_lens(val(), "--focus", true), camera = true;
+        else if (a == "--soft-shadows") soft_params = parse_soft(val()), soft = true;
         else if (a == "-h" || a == "--help") usage(nullptr);
         else if (!a.empty() && a[0] == '-') usage(("unknown option " + a).c_str());
         else if (scenein.empty()) scenein = a;
@@ -254,6 +282,11 @@ int main(int argc, char** argv) {
     if (camera && (passes || groups || adaptive))
         usage("--camera-model, --aperture and --focus render the image alone: not with --passes, --light-groups or --adaptive");
     if (aperture_given && camera_model.model != YRT_CAMERA_PERSPECTIVE) usage("--aperture is the perspective model's lens");
+    if (soft && gpus > 1) usage("--soft-shadows renders on one GPU (--gpus 1)");
+    if (soft && algorithm == YRT_ALGO_MEGAKERNEL)
+        usage("--soft-shadows needs a wavefront algorithm, not --algorithm megakernel");
+    if (soft && (passes || groups || adaptive))
+        usage("--soft-shadows renders the image alone: not with --passes, --light-groups or --adaptive");
     try {
         printf("loading scene %s\n", scenein.c_str());
         auto scn = yrt_cpp::load_scene(scenein);
@@ -323,6 +356,19 @@ int main(int argc, char** argv) {
             const unsigned long long n = yrt_cpp::adaptive_refined(scn);
             printf("adaptive: refined %llu of %llu pixels (%.1f %%)\n", n, (unsigned long long)refined.size(),
                    refined.empty() ? 0.0 : 100.0 * (double)n / (double)refined.size());
+        } else if (soft) {
+            // the image with soft shadows, under the camera model where one is given (else the
+            // pinhole), in host memory
+            yrt_render_params p = scn->params;
+            p.ambient[0] = p.ambient[1] = p.ambient[2] = amb;
+            p.resolution = resolution;
+            p.samples = samples;
+            int w = 0, h = 0;
+            yrt_cpp::check(yrt_image_size(scn->on_device(), &p, &w, &h), "raytrace");
+            hdr = yrt_cpp::image4f(w, h);
+            yrt_cpp::check(yrt_render_soft_shadows(scn->on_device(), &p, camera ? &camera_model : nullptr, &soft_params,
+                                                   &hdr.pixels[0].x, YRT_MEM_HOST, nullptr),
+                           "render_soft_shadows");
         } else if (camera) {
             // the image under the camera model, in host memory
             yrt_render_params p = scn->params;

@@ -18,6 +18,9 @@
 // A ray batch (yrt_shade_rays, run_rays) is the same pipeline with its level 0 from the caller:
 // k_rays_first (the rays as given, the generic closest-hit walk), k_rays_shadow and k_rays_shade
 // (the view point per sample from the ray's own origin), then the levels above; one RGBA per ray.
+// A soft batch (yrt_shade_rays_soft, yrt_render_soft_shadows) is a ray batch whose lights are
+// disks: k_soft_shadow casts K any-hit rays per (hit, light) at every level and leaves the count
+// of open ones, k_soft_shade scales the light's term by the open share.
 //
 // Why: every traversal kernel carries only its ray and stack (few VGPRs, high
 // occupancy), lanes of one wave are 64 samples of one pixel (s=8) or an 8x8 pixel
@@ -37,6 +40,7 @@
 
 #include "item_magic.h"
 #include "packet_trace.h"
+#include "soft_shadow_rays.h"
 #include "trace_common.h"
 #include "wf_workspace.h"
 #include "yrt_render.h"
@@ -1117,6 +1121,116 @@ __global__ __launch_bounds__(shadow_block<PACKET>(), YRT_SHADOW_WAVES) void k_ra
     flush_block<2, BS>(counters, {cnt_shadow_rays, cnt_shadow_culled}, {rays, culled});
 }
 
+// ---- soft shadows (yrt_shade_rays_soft, yrt_render_soft_shadows): K any-hit rays per light ----
+// Every level of a soft ray batch (run_rays with soft_shadow_args). Light li is a disk of radius
+// radius[li] about its point, facing the shading point; a sample that hit casts K rays from its
+// hit point at the disk's points soft_shadow_rays.h gives (the text the host twin
+// tools/check_soft_shadow_rays.cpp evaluates), and the byte of (light, sample) in the occlusion
+// slab receives the number of unoccluded ones, 0..K, instead of k_shadow's flag. A light of radius
+// 0 casts the hard shadow ray itself -- no basis, no offset -- and records K or 0.
+// Level 0 has k_rays_shadow's grid (one block per BS samples and light, the light index minor,
+// dealt in XCD runs) and takes the view point of the zero-term cull from the ray's own origin;
+// levels >= 1 have k_shadow's grid-stride form over the level's segments and take it from the
+// mirror ray's record. K and the light's radius are the same in every lane: the loop over k is a
+// scalar loop and dirs[k] a scalar load (k_ao's), and a wave's 64 rays of one k start at
+// neighbouring hit points and aim at one neighbourhood of the disk, so they walk together.
+// Every lane of a partial wave reaches every walk (valid = false).
+// What stays live across the K walks: p, tp, the two tangents, the rotation and the count -- 17
+// VGPRs beside the walk's own.
+__constant__ float soft_dirs[ao_dir_count * 3] = {YRT_AO_DIRS};
+__constant__ float soft_rots[ao_rot_count * 2] = {YRT_AO_ROTS};
+
+// Six waves per SIMD (80 VGPRs) where k_shadow has eight (64): at 64 the wide walk's own registers
+// leave no room for the 17 and the kernel spilled 9 VGPRs to scratch; at 80 it takes 68 and spills
+// none. The per-lane walk (YRT_ALGO_WAVEFRONT_LANE) needs 110: four waves (128).
+template <bool PACKET>
+constexpr int soft_shadow_waves() { return PACKET ? 6 : 4; }
+template <bool PACKET, typename SE, bool WIDE>
+__global__ __launch_bounds__(shadow_block<PACKET>(), soft_shadow_waves<PACKET>()) void k_soft_shadow(
+    dev_scene_view S, int level, int nsamp_level0, wf_buffers B, unsigned long long* counters, int K,
+    const float* __restrict__ radius) {
+    constexpr int BS = shadow_block<PACKET>();
+    __shared__ traversal_lds<PACKET, SE> lds;
+    auto T = make_tracer<true, false, PACKET, SE>(lds);
+    const unsigned lin = level ? blockIdx.x
+                               : xcd_runs<YRT_SHADOW_LIGHT_MINOR>(blockIdx.y * gridDim.x + blockIdx.x,
+                                                                  gridDim.x * gridDim.y);
+    const int li = level ? (int)blockIdx.y : (int)(lin % gridDim.y);
+    const int bx = level ? (int)blockIdx.x : (int)(lin / gridDim.y);
+    const f4* lr = S.lights + 6 * li;
+    const frame3f lf = {xyz(ld4(lr)), xyz(ld4(lr + 1)), xyz(ld4(lr + 2)), xyz(ld4(lr + 3))};
+    const vec3f lp0 = xyz(ld4(lr + 4)), ke = xyz(ld4(lr + 5));
+    const float R = radius[li];
+    const bool hard = R == 0.0f;
+    const unsigned long long per_pair = hard ? 1ull : (unsigned long long)K;  // rays a (hit sample, light) pair counts
+    work_counts wc;
+    unsigned long long rays = 0, culled = 0;  // culled: counted in rays, answered without a walk
+    const int stride = gridDim.x * BS;
+    for (int g = 0; g < (level ? level_segments : 1); g++) {
+    const int n = level ? *seg_counter(B.count, level, g) : nsamp_level0;
+    const int nround = (n + stride - 1) / stride;
+    for (int round = 0; round < nround; round++) {
+        const int j = round * stride + bx * BS + (int)threadIdx.x;
+        const int idx = g * B.seg + j;
+        bool valid = false;
+        int info = -1;
+        float r = 1.0f;
+        float4 s1 = {0, 0, 0, 0};
+        vec3f ro = {0, 0, 0}, p = {0, 0, 0}, tp = {0, 0, 1}, l = {0, 0, 1};
+        if (j < n) {
+            const float4 s0 = ld4s(B.surf0 + idx);
+            s1 = ld4s(B.surf1 + idx);  // n and the view point, for light_term_zero
+            ro = level ? xyz(ld4(B.ray_o(level) + idx)) : ray_origin(B, idx);
+            info = sample_state(s0);
+            if (info >= 0) {
+                p = xyz(s0);
+                tp = transform_point(lf, lp0 - p);
+                normalize_len(tp, l, r);
+                valid = true;
+                rays += per_pair;
+            }
+        }
+        // (uniform control flow; a lane that is not a hit has info < 0)
+        if (light_term_zero(info, xyz(s1), p, ro, l, r, ke)) {
+            stb(B.occl + (size_t)li * B.capacity + idx, 0);
+            valid = false;
+            culled += per_pair;
+        }
+        hit_record hr;
+        int open = 0;
+        if (hard) {  // (uniform over the block) the hard shadow ray, bit for bit
+            const ray3 sr = {p, l, 0.01f, r - 0.01f};
+            bool occ;
+            if constexpr (WIDE)
+                occ = packet_occluded_wide2(S, sr, valid);
+            else
+                occ = T.trace(S, sr, valid, hr, wc);
+            open = occ ? 0 : K;
+        } else {
+            const int rot = soft_shadow_rot(p, li);
+            const float c = soft_rots[2 * rot], sn = soft_rots[2 * rot + 1];
+            vec3f b1, b2;
+            soft_shadow_basis(l, b1, b2);
+            for (int k = 0; k < K; k++) {
+                const vec3f tq = soft_shadow_target(tp, b1, b2, c, sn, soft_dirs, k, R);
+                vec3f lq;
+                float rq;
+                normalize_len(tq, lq, rq);
+                const ray3 sr = {p, lq, 0.01f, rq - 0.01f};
+                bool occ;
+                if constexpr (WIDE)
+                    occ = packet_occluded_wide2(S, sr, valid);
+                else
+                    occ = T.trace(S, sr, valid, hr, wc);
+                open += valid && !occ ? 1 : 0;
+            }
+        }
+        if (valid) stb(B.occl + (size_t)li * B.capacity + idx, (unsigned char)open);
+    }
+    }
+    flush_block<2, BS>(counters, {cnt_shadow_rays, cnt_shadow_culled}, {rays, culled});
+}
+
 // The hull of box P = [P0, P1] and the point Lp, as the 16 lanes of a slot group hold it:
 // lane j = lane % 16, j == 0 the hull's box (P's box with Lp), j = 1..12 the plane through
 // Lp and box edge j - 1 of P when that edge is on P's silhouette seen from Lp (one adjacent
@@ -2093,20 +2207,30 @@ struct pass_terms {
     // max_depth cuts it (0 * kr), la. A sample that never gets here keeps +0 in each.
     vec3f c = {0, 0, 0}, d = {0, 0, 0}, s = {0, 0, 0}, r = {0, 0, 0}, la = {0, 0, 0};
 };
+// SOFT (soft shadows, k_soft_shade): a light's occlusion record is its count of unoccluded rays
+// out of soft->rays (k_soft_shadow; OCC4: byte li of occ_bits), a light with none is skipped and
+// every other term is scaled by float(open) / float(rays); with the default, an empty type,
+// nothing of it is compiled.
+struct no_soft {};
+struct soft_factor {
+    int rays;  // K
+};
 __device__ __forceinline__ vec3f amb_of(const vec3f& a) { return a; }
 __device__ __forceinline__ vec3f amb_of(const float* a) { return {a[0], a[1], a[2]}; }  // (LATE: read where it is used)
-template <bool COUNT, bool FUSE, bool OCC4, bool LATE = false, class AMB = vec3f, class TERMS = no_terms>
+template <bool COUNT, bool FUSE, bool OCC4, bool LATE = false, class AMB = vec3f, class TERMS = no_terms,
+          class SOFT = no_soft>
 __device__ __forceinline__ void shade_hit(const dev_scene_view& S, const wf_buffers& B, int idx, int info,
                                           const float4& s0, const float4& ro4, uint32_t occ_bits, int level,
                                           int max_depth, const AMB& amb, const float* lut, work_counts& wc,
                                           unsigned long long& truncated, vec3f& R, vec3f& p, bool& spawn, vec3f& dr,
                                           vec3f& rec_d, vec3f& rec_la, int& rec_mat, bool& write_r,
                                           TERMS* terms = nullptr, const float4* carried = nullptr,
-                                          int ncarried = 0) {
+                                          int ncarried = 0, const SOFT* soft = nullptr) {
     // carried (k_shadow_shade_persist, YRT_LIGHT_CARRY): this lane's {l, r} of light li at
     // carried[li * 64], for li < ncarried -- the values the light loop computes, from the same
     // statements on the same p (shadow_item_light)
     constexpr bool SPLIT = !std::is_same<TERMS, no_terms>::value;
+    constexpr bool AREA = !std::is_same<SOFT, no_soft>::value;
     vec3f nrm;
     vec2f uv;
     int mat, kind;
@@ -2141,7 +2265,13 @@ __device__ __forceinline__ void shade_hit(const dev_scene_view& S, const wf_buff
     float vlen;
     normalize_len(ro - p, v, vlen);
     for (int li = 0; li < S.nlights; li++) {
-        if (OCC4 ? ((occ_bits >> li) & 1u) != 0u : ldb(B.occl + (size_t)li * B.capacity + idx) != 0) continue;
+        uint32_t open = 0;  // (AREA) the light's unoccluded rays
+        if constexpr (AREA) {
+            open = OCC4 ? (occ_bits >> (8 * li)) & 0xffu : (uint32_t)ldb(B.occl + (size_t)li * B.capacity + idx);
+            if (open == 0u) continue;
+        } else {
+            if (OCC4 ? ((occ_bits >> li) & 1u) != 0u : ldb(B.occl + (size_t)li * B.capacity + idx) != 0) continue;
+        }
         const f4* lr = S.lights + 6 * li;
         vec3f l, ke;
         float r;
@@ -2160,7 +2290,10 @@ __device__ __forceinline__ void shade_hit(const dev_scene_view& S, const wf_buff
         if (ks_txt >= 0) ks = ks * tks;
         vec3f ld, ls;
         light_term(kind, nrm, v, l, r, ke, kd, ks, ns, ld, ls);
-        c = c + (ld + ls);
+        if constexpr (AREA)
+            c = c + (ld + ls) * (float(open) / float(soft->rays));
+        else
+            c = c + (ld + ls);
         if constexpr (SPLIT) terms->d = terms->d + ld, terms->s = terms->s + ls;
     }
     if (LATE) {
@@ -2300,11 +2433,15 @@ struct pass_buffers {
 // RGBA per ray
 // PASSES (the unfused k_shade_passes; P its planes): the terms of each camera sample go to
 // P.smp, the reflection term of a sample with a mirror ray where the fold reaches it
-template <bool COUNT, bool FUSE, int SB, bool OCC4, bool RAYS, bool PASSES = false>
+// SOFT (a soft ray batch, k_soft_shade; soft_rays its K): the occlusion bytes are counts of
+// unoccluded rays, with OCC4 four of them in occ_bits, and shade_hit scales each light's term
+template <bool COUNT, bool FUSE, int SB, bool OCC4, bool RAYS, bool PASSES = false, bool SOFT = false>
 __device__ __forceinline__ void shade_samples(dev_scene_view S, dev_render_args A, int level, int nsamp_level0,
                                               int max_depth, wf_buffers B, unsigned long long* counters, chunk_args C,
-                                              float4* __restrict__ out, const pass_buffers* P = nullptr) {
+                                              float4* __restrict__ out, const pass_buffers* P = nullptr,
+                                              int soft_rays = 0) {
     static_assert(!(PASSES && FUSE), "the fused passes kernel has its own body");
+    static_assert(!SOFT || (RAYS && !PASSES && !FUSE && !COUNT), "soft shadows shade ray batches");
     __shared__ float4 fused_rad[FUSE ? SB : 1];
     __shared__ int cmp_count[SB / 64], cmp_base[SB / 64];
     __shared__ srgb_table srgb_lds;
@@ -2339,7 +2476,10 @@ __device__ __forceinline__ void shade_samples(dev_scene_view S, dev_render_args 
                 for (int q = 0; q < 4; q++) {
                     const int lq = q < S.nlights ? q : 0;  // an unconditional load, masked after
                     const uint32_t ob = ldb(B.occl + (size_t)lq * B.capacity + idx);
-                    occ_bits |= (q < S.nlights && ob != 0u) ? 1u << q : 0u;
+                    if constexpr (SOFT)
+                        occ_bits |= q < S.nlights ? ob << (8 * q) : 0u;
+                    else
+                        occ_bits |= (q < S.nlights && ob != 0u) ? 1u << q : 0u;
                 }
             }
             const int info = sample_state(s0);
@@ -2357,9 +2497,16 @@ __device__ __forceinline__ void shade_samples(dev_scene_view S, dev_render_args 
             // empty object and a null pointer: with its address k_shade came out differently)
             typename std::conditional<PASSES, pass_terms, no_terms>::type T;
             if (info >= 0) {
-                shade_hit<COUNT, FUSE, OCC4>(S, B, idx, info, s0, ro4, occ_bits, level, max_depth, amb, lut, wc,
-                                             truncated, R, p, spawn, dr, rec_d, rec_la, rec_mat, write_r,
-                                             PASSES ? &T : nullptr);
+                if constexpr (SOFT) {
+                    const soft_factor F = {soft_rays};
+                    shade_hit<COUNT, FUSE, OCC4, false, vec3f, no_terms, soft_factor>(
+                        S, B, idx, info, s0, ro4, occ_bits, level, max_depth, amb, lut, wc, truncated, R, p, spawn, dr,
+                        rec_d, rec_la, rec_mat, write_r, nullptr, nullptr, 0, &F);
+                } else {
+                    shade_hit<COUNT, FUSE, OCC4>(S, B, idx, info, s0, ro4, occ_bits, level, max_depth, amb, lut, wc,
+                                                 truncated, R, p, spawn, dr, rec_d, rec_la, rec_mat, write_r,
+                                                 PASSES ? &T : nullptr);
+                }
             }
             if constexpr (PASSES) {
                 if (level == 0 && info != -2) {
@@ -2443,6 +2590,20 @@ __global__ __launch_bounds__(WF_BLOCK, YRT_SHADE_LEVEL_WAVES) void k_rays_shade(
     A.amb[0] = amb3.x, A.amb[1] = amb3.y, A.amb[2] = amb3.z;
     const chunk_args C = {0, nsamp_level0, 1, 1};
     shade_samples<false, false, WF_BLOCK, OCC4, true>(S, A, level, nsamp_level0, max_depth, B, counters, C, nullptr);
+}
+
+// every level of a soft ray batch (run_rays with soft_shadow_args): k_rays_shade with the
+// occlusion bytes read as k_soft_shadow's counts of unoccluded rays out of K
+template <bool OCC4>
+__global__ __launch_bounds__(WF_BLOCK, YRT_SHADE_LEVEL_WAVES) void k_soft_shade(dev_scene_view S, float3 amb3, int level,
+                                                                                int nsamp_level0, int max_depth,
+                                                                                wf_buffers B,
+                                                                                unsigned long long* counters, int K) {
+    dev_render_args A = {};
+    A.amb[0] = amb3.x, A.amb[1] = amb3.y, A.amb[2] = amb3.z;
+    const chunk_args C = {0, nsamp_level0, 1, 1};
+    shade_samples<false, false, WF_BLOCK, OCC4, true, false, true>(S, A, level, nsamp_level0, max_depth, B, counters, C,
+                                                                   nullptr, nullptr, K);
 }
 
 // the shading passes (yrt_render_passes). Unfused (mirror levels, or pixels that are not whole
@@ -3187,13 +3348,13 @@ constexpr int stride_grid = 2048;  // grid-stride kernels: 8 blocks of 256 per C
 // mirror rays ends the chunk's recursion. The level's k_bounce is queued before the host waits
 // for the level's ray count, so the GPU works on it while the count comes back; only a level
 // that turns out empty costs a launch (one k_bounce of no rays).
-// shadow0(): launches level 0's shadow rays where the caller has a kernel of its own for them;
-// false: they run on the k_shadow grid like every later level's.
+// shadow(level): launches the level's shadow rays where the caller has a kernel of its own for
+// them; false: they run on the k_shadow grid.
 // shade(level, grid): launches the kernel that shades a level.
-// level0_shaded: shadow0's kernel has shaded level 0 too.
-template <bool COUNT, bool PACKET, typename SE, class SHADOW0, class SHADE>
+// level0_shaded: the caller's shadow kernel has shaded level 0 too.
+template <bool COUNT, bool PACKET, typename SE, class SHADOW, class SHADE>
 hipError_t run_levels(device_scene& ds, const wf_buffers& B, int nlevels, int nsamp, const float4& cam4,
-                      unsigned long long* counters, hipStream_t stream, SHADOW0&& shadow0, bool level0_shaded,
+                      unsigned long long* counters, hipStream_t stream, SHADOW&& shadow, bool level0_shaded,
                       SHADE&& shade) {
     phase_timer& T = ds.timer;
     constexpr int TB = shadow_block<PACKET>();
@@ -3209,7 +3370,7 @@ hipError_t run_levels(device_scene& ds, const wf_buffers& B, int nlevels, int ns
         }
         if (ds.nlights > 0) {
             int t = T.begin(phase_shadow, stream);
-            if (level > 0 || !shadow0()) {
+            if (!shadow(level)) {
                 const dim3 sg(level ? stride_grid * WF_BLOCK / TB : (nsamp + TB - 1) / TB, ds.nlights);
                 with_bool(!COUNT && PACKET && ds.wide_ok, [&](auto wide) {
                     hipLaunchKernelGGL((k_shadow<COUNT, PACKET, SE, decltype(wide)::value>), sg, dim3(TB), 0, stream,
@@ -3354,8 +3515,8 @@ hipError_t run(device_scene& ds, const dev_render_args& A, float4* out, unsigned
         }
         // level 0 only: at c3 the mirror levels' compacted samples trace faster with the
         // hardware's dealing (shadow 1.64 -> 1.72 ms with them persistent)
-        auto shadow0 = [&] {
-            if (!shadow_persist) return false;
+        auto shadow = [&](int level) {
+            if (level > 0 || !shadow_persist) return false;
             // one resident grid: two 1024-thread blocks per CU (8 waves per SIMD)
             // (its work counters B.queue[0, 9) were zeroed by k_chunk_setup)
             const int nb = ds.num_cus * (YRT_SHADOW_WAVES * 4 * 64 / SP_BLOCK);
@@ -3395,7 +3556,7 @@ hipError_t run(device_scene& ds, const dev_render_args& A, float4* out, unsigned
             });
         };
         // (shadow_shade: k_shadow_shade_persist has shaded the chunk and written its pixels)
-        if (hipError_t e = run_levels<COUNT, PACKET, SE>(ds, B, nlevels, nsamp, cam4, counters, stream, shadow0,
+        if (hipError_t e = run_levels<COUNT, PACKET, SE>(ds, B, nlevels, nsamp, cam4, counters, stream, shadow,
                                                          shadow_shade, shade);
             e != hipSuccess)
             return e;
@@ -3437,9 +3598,11 @@ hipError_t run(device_scene& ds, const dev_render_args& A, float4* out, unsigned
 // origin), so the tile-list mode and the LDS staging of the handle change nothing here and the
 // handle reports neither as used. The mirror levels, the fold and the workspace are run()'s;
 // the fold's last step writes the ray's colour straight into `out` (B.rad), in batch order.
+// soft (yrt_shade_rays_soft): every level's shadow rays are k_soft_shadow's K rays per light and
+// its shading k_soft_shade's; null: yrt_shade_rays
 template <bool PACKET, typename SE>
 hipError_t run_rays(device_scene& ds, const dev_render_args& A, const float* rays, int n, float4* out,
-                    unsigned long long* counters, hipStream_t stream) {
+                    unsigned long long* counters, hipStream_t stream, const soft_shadow_args* soft = nullptr) {
     chunk_plan plan;
     if (hipError_t e = plan_chunks(ds, A, n, 1, 1, nullptr, nullptr, plan); e != hipSuccess) return e;
     wf_buffers& B = plan.B;
@@ -3460,21 +3623,31 @@ hipError_t run_rays(device_scene& ds, const dev_render_args& A, const float* ray
         hipLaunchKernelGGL((k_rays_first<PACKET, SE>), dim3((nsamp + WF_BLOCK - 1) / WF_BLOCK), dim3(WF_BLOCK), 0,
                            stream, ds.view, nsamp, B, counters);
         T.end(t, stream);
-        auto shadow0 = [&] {
+        auto shadow = [&](int level) {
+            if (level > 0 && !soft) return false;
             with_bool(PACKET && ds.wide_ok, [&](auto wide) {
                 constexpr bool WIDE = PACKET && decltype(wide)::value;  // (no wide per-lane walk)
-                hipLaunchKernelGGL((k_rays_shadow<PACKET, SE, WIDE>), dim3((nsamp + TB - 1) / TB, ds.nlights),
-                                   dim3(TB), 0, stream, ds.view, nsamp, B, counters);
+                if (soft) {
+                    const dim3 sg(level ? stride_grid * WF_BLOCK / TB : (nsamp + TB - 1) / TB, ds.nlights);
+                    hipLaunchKernelGGL((k_soft_shadow<PACKET, SE, WIDE>), sg, dim3(TB), 0, stream, ds.view, level, nsamp,
+                                       B, counters, soft->rays, soft->radius);
+                } else
+                    hipLaunchKernelGGL((k_rays_shadow<PACKET, SE, WIDE>), dim3((nsamp + TB - 1) / TB, ds.nlights),
+                                       dim3(TB), 0, stream, ds.view, nsamp, B, counters);
             });
             return true;
         };
         auto shade = [&](int level, dim3 grid) {
             with_bool(ds.nlights <= 4, [&](auto occ4) {
-                hipLaunchKernelGGL(k_rays_shade<decltype(occ4)::value>, grid, dim3(WF_BLOCK), 0, stream, ds.view, amb3,
-                                   level, nsamp, A.max_depth, B, counters);
+                if (soft)
+                    hipLaunchKernelGGL(k_soft_shade<decltype(occ4)::value>, grid, dim3(WF_BLOCK), 0, stream, ds.view,
+                                       amb3, level, nsamp, A.max_depth, B, counters, soft->rays);
+                else
+                    hipLaunchKernelGGL(k_rays_shade<decltype(occ4)::value>, grid, dim3(WF_BLOCK), 0, stream, ds.view,
+                                       amb3, level, nsamp, A.max_depth, B, counters);
             });
         };
-        if (hipError_t e = run_levels<false, PACKET, SE>(ds, B, plan.nlevels, nsamp, cam4, counters, stream, shadow0,
+        if (hipError_t e = run_levels<false, PACKET, SE>(ds, B, plan.nlevels, nsamp, cam4, counters, stream, shadow,
                                                          false, shade);
             e != hipSuccess)
             return e;
@@ -3485,11 +3658,33 @@ hipError_t run_rays(device_scene& ds, const dev_render_args& A, const float* ray
 }  // namespace
 
 hipError_t launch_shade_rays_wavefront(device_scene& ds, const dev_render_args& args, const float* rays, int n,
-                                       void* out_rgba, unsigned long long* counters, bool packet, hipStream_t stream) {
+                                       void* out_rgba, unsigned long long* counters, bool packet, hipStream_t stream,
+                                       const soft_shadow_args* soft) {
     if (n <= 0) return clear_counters(counters, stream);  // (no chunk)
+    if (soft && (soft->rays < 1 || soft->rays > soft_shadow_rays_max || (ds.nlights > 0 && !soft->radius)))
+        return hipErrorInvalidValue;
     return with_walk(ds, packet, [&](auto pk, auto se) {
-        return run_rays<decltype(pk)::value, decltype(se)>(ds, args, rays, n, (float4*)out_rgba, counters, stream);
+        return run_rays<decltype(pk)::value, decltype(se)>(ds, args, rays, n, (float4*)out_rgba, counters, stream,
+                                                           soft);
     });
+}
+
+hipError_t upload_soft_shadow_radii(device_scene& ds, const float* radius, float all, hipStream_t stream) {
+    ds.soft_radius_host.assign((size_t)ds.nlights, all);
+    if (radius) std::copy(radius, radius + ds.nlights, ds.soft_radius_host.begin());
+    if (ds.nlights == 0) return hipSuccess;
+    if (!ds.soft_radius) {  // (a scene's light count is fixed)
+        if (hipError_t e = hipMalloc((void**)&ds.soft_radius, sizeof(float) * (size_t)ds.nlights); e != hipSuccess) return e;
+    }
+    // One stream at a time per handle, as for the workspace (ds.work) and the groups' table
+    // (ds.group_tab): the device array and its host source are the handle's, so two soft calls of
+    // one handle on different streams would share them. Within a stream the order is safe: the
+    // source is pageable memory, for which hipMemcpyAsync copies it into the runtime's staging
+    // buffer before it returns (the documented behaviour of a pageable host-to-device copy), so
+    // the next call may overwrite soft_radius_host; the device array is rewritten in stream order,
+    // behind the kernels of the call before.
+    return hipMemcpyAsync(ds.soft_radius, ds.soft_radius_host.data(), sizeof(float) * (size_t)ds.nlights,
+                          hipMemcpyHostToDevice, stream);
 }
 
 hipError_t launch_render_wavefront(device_scene& ds, const dev_render_args& args, void* out_rgba,

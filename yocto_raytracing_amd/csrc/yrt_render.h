@@ -96,6 +96,10 @@ struct device_scene {
     unsigned long long* adaptive_count_host = nullptr;
     hipEvent_t adaptive_count_ev = nullptr;
     unsigned long long adaptive_refined = 0;
+    // soft shadows (upload_soft_shadow_radii): the last call's radius per light, on the host (the
+    // source of its copy) and on the device (nlights floats, allocated by the first soft call)
+    std::vector<float> soft_radius_host;
+    float* soft_radius = nullptr;
     phase_timer timer;
 };
 
@@ -184,8 +188,20 @@ hipError_t launch_render_wavefront(device_scene& ds, const dev_render_args& args
 // tmin, tmax} and out n x RGBA f32, both device pointers; args carries amb and max_depth only.
 // The wavefront pipeline in ray mode (wavefront.hip run_rays: k_rays_first as level 0, then the
 // render's levels; counters zeroed in its first kernel, timings per phase) ...
+// With `soft` (yrt_shade_rays_soft) every light is a disk: K = soft->rays any-hit rays per (hit
+// sample, light) at every level (k_soft_shadow), the light's term scaled by the unoccluded share
+// (k_soft_shade). soft->radius is device memory, a radius per light (upload_soft_shadow_radii).
+constexpr int soft_shadow_rays_max = 64;  // a ray per entry of the table (ao_tables.h)
+struct soft_shadow_args {
+    int rays;             // K, 1..soft_shadow_rays_max
+    const float* radius;  // device: nlights radii, each >= 0 and finite; 0 is the point light
+};
 hipError_t launch_shade_rays_wavefront(device_scene& ds, const dev_render_args& args, const float* rays, int n,
-                                       void* out_rgba, unsigned long long* counters, bool packet, hipStream_t stream);
+                                       void* out_rgba, unsigned long long* counters, bool packet, hipStream_t stream,
+                                       const soft_shadow_args* soft = nullptr);
+// the call's radii into ds.soft_radius, in stream order: radius[nlights] (host), or `all` for
+// every light when radius is null
+hipError_t upload_soft_shadow_radii(device_scene& ds, const float* radius, float all, hipStream_t stream);
 // ... or one lane per ray through the megakernel's shade_path (render.hip; the caller zeroes
 // the counters and caps max_depth at megakernel_max_depth)
 hipError_t launch_shade_rays(device_scene& ds, const dev_render_args& args, const float* rays, int n, void* out_rgba,
@@ -251,6 +267,11 @@ hipError_t launch_render_adaptive(device_scene& ds, const dev_render_args& args,
 hipError_t launch_render_camera(device_scene& ds, const dev_render_args& args, int model, float aperture,
                                 int chunk_pixels, void* out_rgba, unsigned long long* counters, bool packet,
                                 hipStream_t stream);
+// yrt_render_soft_shadows: launch_render_camera with the soft batch shader
+// (launch_shade_rays_wavefront with `soft`): the same chunks and resolve, any camera model
+hipError_t launch_render_soft_shadows(device_scene& ds, const dev_render_args& args, int model, float aperture,
+                                      int chunk_pixels, const soft_shadow_args& soft, void* out_rgba,
+                                      unsigned long long* counters, bool packet, hipStream_t stream);
 // k_camera_rays alone over the whole window (which lies inside the image), tile_w * tile_h *
 // samples^2 records of 32 bytes into `rays` (device memory); touches no counter
 hipError_t launch_camera_rays(device_scene& ds, const dev_render_args& args, int model, float aperture, void* rays,
