@@ -131,12 +131,17 @@ def test_the_models_edge_cases():
 
 
 def test_adaptive_kernels_code_object_budget():
-    """the flag, ray and resolve kernels (and the counter add) keep everything in registers"""
+    """the flag kernel and the pixel-batch kernels the refinement runs on (camera.hip: a
+    k_camera_rays per camera model and k_camera_resolve, each once, with the list argument) keep
+    everything in registers; the kernels that the shared ones replaced are gone"""
     from yocto_raytracing_amd.codeid import kernel_resources
 
-    new = {k: v for k, v in kernel_resources(LIB).items() if "k_adaptive_" in k}
-    for name in ("k_adaptive_flag", "k_adaptive_rays", "k_adaptive_resolve"):
-        assert len([k for k in new if name in k]) == 1, (name, sorted(new))
+    res = kernel_resources(LIB)
+    new = {k: v for k, v in res.items() if "k_adaptive_" in k or "k_camera_rays" in k or "k_camera_resolve" in k}
+    for name, count in (("k_adaptive_flag", 1), ("k_camera_rays", 3), ("k_camera_resolve", 1),
+                        ("k_adaptive_rays", 0), ("k_adaptive_resolve", 0), ("k_adaptive_add_counters", 0)):
+        assert len([k for k in new if name in k]) == count, (name, sorted(new))
+    assert len(new) == 5, sorted(new)
     for name, r in new.items():
         print(f"{name[:48]}: {r['vgpr']} VGPRs, {r['sgpr']} SGPRs, {r['lds']} B LDS, block {r['block']}")
         assert r["vgpr_spill"] == 0 and r["sgpr_spill"] == 0 and r["private"] == 0, (name, r)

@@ -1,7 +1,7 @@
 """yrt_render_adaptive on the GPU: a base frame at b*b samples per pixel, the contrast rule of
 include/yrt.h between neighbouring pixels of it, and yrt_render's own s*s-sample value in the
-pixels the rule flags (adaptive.hip: k_adaptive_flag, k_adaptive_rays, the ray-batch pipeline,
-k_adaptive_resolve).
+pixels the rule flags (adaptive.hip: k_adaptive_flag; camera.hip: the pixel-batch pipeline over
+the flagged list, k_camera_rays as the pinhole, the ray-batch driver, k_camera_resolve).
 
 Frames of 37 x 24 and 24 x 37 pixels (partial waves, partial tiles), s = 3, b = 1. Every
 expectation is bit for bit. The rule's numpy model (tests/adaptive_model.py) is applied to the

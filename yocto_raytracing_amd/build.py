@@ -29,10 +29,10 @@ ARCH = os.environ.get("YRT_OFFLOAD_ARCH", "gfx950")
 SOURCES = ["obj_loader.cpp", "png.cpp", "scene_io.cpp", "bvh_build.cpp",
            "device_scene.cpp", "capi.cpp", "multi.cpp", "render.hip", "wavefront.hip", "bvh_gpu.hip"]
 # device sources that are part of another one's translation unit: render.hip ends by including
-# aov.hip (the AOV pass), mattes.hip (the ID-matte pass), adaptive.hip (adaptive
-# supersampling), ao.hip (ambient occlusion) and camera.hip (camera models), so the library keeps one gfx950
-# code object per entry of SOURCES
-INCLUDED = {"render.hip": ["aov.hip", "mattes.hip", "adaptive.hip", "ao.hip", "camera.hip"]}
+# aov.hip (the AOV pass), mattes.hip (the ID-matte pass), ao.hip (ambient occlusion), camera.hip
+# (camera models and the pixel batches) and adaptive.hip (adaptive supersampling), so the library
+# keeps one gfx950 code object per entry of SOURCES
+INCLUDED = {"render.hip": ["aov.hip", "mattes.hip", "ao.hip", "camera.hip", "adaptive.hip"]}
 COMMON = ["-O3", "-fPIC", "-std=c++17", "-ffp-contract=off", "-Wall", "-Wno-unused-function",
           f"-I{CSRC}", f"-I{ROOT / 'include'}"]
 

@@ -1,8 +1,9 @@
 // adaptive.hip -- adaptive supersampling (yrt_render_adaptive): Whitted's own answer to the
 // cost of s*s camera samples in every pixel. A base frame at b*b samples per pixel, a contrast
 // test between neighbouring pixels of that frame, and the full s*s samples only in the pixels
-// the test flags. render.hip includes this file after mattes.hip: the feature's kernels are a
-// part of that translation unit and of its gfx950 code object.
+// the test flags. render.hip includes this file after camera.hip: the feature's kernels are a
+// part of that translation unit and of its gfx950 code object, and the refinement runs on
+// camera.hip's pixel-batch pipeline (render_pixel_batches, with grow_scratch and scratch_align).
 //
 // The contract (include/yrt.h): B is yrt_render's frame at `base` samples per
 // axis, over the window grown by one pixel on every side and clipped to the image (the apron;
@@ -11,15 +12,15 @@
 // threshold, in float32, an IEEE comparison (false on NaN). A flagged pixel receives exactly
 // yrt_render's value at s samples per axis, every other pixel B.
 //
-// The refined pixels are shaded as a ray batch (wavefront.hip run_rays, through
-// launch_shade_rays_wavefront): k_adaptive_rays writes a chunk's camera rays, a pixel's s*s
-// samples consecutive with jj outer and ii inner, the batch shades them, k_adaptive_resolve
-// sums each pixel's colours in that order. A pixel's value depends on its own rays alone, so
-// neither the order of the flagged list (an atomic per block) nor the chunk size changes a bit.
+// The refined pixels are the flagged list through render_pixel_batches with the pinhole camera:
+// camera_perspective at aperture 0 is camera_ray's expression term for term (camera_models.h),
+// so a refined pixel is yrt_render's. A pixel's value depends on its own rays alone, so neither
+// the order of the flagged list (an atomic per block) nor the chunk size changes a bit.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 
+#include "camera_models.h"
 #include "trace_common.h"
 #include "yrt_render.h"
 
@@ -27,7 +28,6 @@ namespace yrt {
 namespace {
 
 constexpr int AD_BLOCK_X = 64, AD_BLOCK_Y = 4;  // k_adaptive_flag: a wave is 64 pixels of one row
-constexpr int AD_BLOCK = 256;                   // the one-dimensional kernels
 
 // the base frame B: the grown window's pixels, row-major, gw per row, from image pixel (gx0, gy0)
 struct adaptive_base {
@@ -95,62 +95,6 @@ __global__ __launch_bounds__(AD_BLOCK_X * AD_BLOCK_Y) void k_adaptive_flag(dev_r
     }
 }
 
-// One lane per camera ray of a chunk of npix flagged pixels: ray r is sample r % spp (jj outer,
-// ii inner) of pixel list[r / spp], camera_ray's bits with its tmin and tmax (k_primary's), as
-// two 16-byte stores of the 32-byte record {o.xyz, d.xyz, tmin, tmax}.
-__global__ __launch_bounds__(AD_BLOCK) void k_adaptive_rays(dev_render_args A, const unsigned* __restrict__ list,
-                                                            int npix, float4* __restrict__ rays) {
-    const int ns = A.samples, spp = ns * ns;
-    const long long r = (long long)blockIdx.x * AD_BLOCK + threadIdx.x;
-    if (r >= (long long)npix * spp) return;
-    const int k = (int)(r / spp), q = (int)(r % spp);
-    const unsigned p = list[k];
-    const int i = A.x0 + (int)(p % (unsigned)A.tile_w), j = A.y0 + (int)(p / (unsigned)A.tile_w);
-    const ray3 ray = camera_ray(A.cam, A.width, A.height, ns, i, j, q % ns, q / ns);
-    rays[2 * r] = make_float4(ray.o.x, ray.o.y, ray.o.z, ray.d.x);
-    rays[2 * r + 1] = make_float4(ray.d.y, ray.d.z, ray.tmin, ray.tmax);
-}
-
-// One lane per flagged pixel of the chunk: the float32 sum of its spp colours in sample order
-// from +0, divided by float(spp), .w = 1 (wavefront.hip accumulate_plane), into its place in out.
-__global__ __launch_bounds__(AD_BLOCK) void k_adaptive_resolve(dev_render_args A, const unsigned* __restrict__ list,
-                                                               int npix, const float4* __restrict__ colours,
-                                                               float4* __restrict__ out) {
-    const int k = blockIdx.x * AD_BLOCK + threadIdx.x;
-    if (k >= npix) return;
-    const int spp = A.samples * A.samples;
-    const float4* c = colours + (size_t)k * spp;
-    vec3f acc = {0, 0, 0};
-    for (int q = 0; q < spp; q++) {
-        const float4 v = c[q];
-        acc = {acc.x + v.x, acc.y + v.y, acc.z + v.z};
-    }
-    const unsigned p = list[k];
-    const size_t at = (size_t)(p / (unsigned)A.tile_w) * A.out_stride + p % (unsigned)A.tile_w;
-    const float d = float(spp);
-    out[at] = make_float4(acc.x / d, acc.y / d, acc.z / d, 1.0f);
-}
-
-// a batch zeroes the counter lines in its first kernel: the call's counts so far, saved before
-// the batch, are added back after it
-__global__ __launch_bounds__(AD_BLOCK) void k_adaptive_add_counters(unsigned long long* __restrict__ counters,
-                                                                    const unsigned long long* __restrict__ saved) {
-    const int k = blockIdx.x * AD_BLOCK + threadIdx.x;
-    if (k < cnt_slots * cnt_count) counters[k] += saved[k];
-}
-
-size_t adaptive_align(size_t x) { return (x + 255) & ~size_t(255); }
-
-hipError_t grow(void*& buf, size_t& have, size_t need) {
-    if (need <= have) return hipSuccess;
-    if (buf) (void)hipFree(buf);
-    buf = nullptr;
-    have = 0;
-    const hipError_t e = hipMalloc(&buf, need);
-    if (e == hipSuccess) have = need;
-    return e;
-}
-
 }  // namespace
 
 hipError_t launch_render_adaptive(device_scene& ds, const dev_render_args& args, int base_samples, float threshold,
@@ -160,7 +104,6 @@ hipError_t launch_render_adaptive(device_scene& ds, const dev_render_args& args,
     if (args.tile_w <= 0 || args.tile_h <= 0) {  // an empty window: nothing written, nothing counted
         return hipMemsetAsync(counters, 0, (size_t)cnt_slots * cnt_count * sizeof(unsigned long long), stream);
     }
-    const int spp = args.samples * args.samples;
     if ((long long)args.tile_w * args.tile_h > (1ll << 31) - 1)
         throw unsupported_error("adaptive supersampling indexes a window's pixels in 31 bits");
     // the apron: the window's image rows and columns, grown by one pixel and clipped to the image
@@ -172,18 +115,16 @@ hipError_t launch_render_adaptive(device_scene& ds, const dev_render_args& args,
     base.tile_w = std::min(args.x0 + args.tile_w + 1, args.width) - base.x0;
     base.tile_h = std::min(args.y0 + rows + 1, args.height) - base.y0;
     base.out_stride = base.tile_w;
-    // the frame scratch: the flagged count, the saved counter lines, the base frame, the list
-    const size_t counter_bytes = (size_t)cnt_slots * cnt_count * sizeof(unsigned long long);
-    const size_t base_bytes = adaptive_align((size_t)base.tile_w * base.tile_h * sizeof(float4));
-    const size_t list_bytes = adaptive_align((size_t)args.tile_w * rows * sizeof(unsigned));
-    if (hipError_t e = grow(ds.adaptive_frame, ds.adaptive_frame_bytes, 256 + counter_bytes + base_bytes + list_bytes);
+    // the frame scratch: the flagged count, the base frame, the list
+    const size_t base_bytes = scratch_align((size_t)base.tile_w * base.tile_h * sizeof(float4));
+    const size_t list_bytes = scratch_align((size_t)args.tile_w * rows * sizeof(unsigned));
+    if (hipError_t e = grow_scratch(ds.adaptive_frame, ds.adaptive_frame_bytes, 256 + base_bytes + list_bytes);
         e != hipSuccess)
         return e;
     char* at = (char*)ds.adaptive_frame;
     unsigned long long* count = (unsigned long long*)at;
-    unsigned long long* saved = (unsigned long long*)(at + 256);
-    float4* base_px = (float4*)(at + 256 + counter_bytes);
-    unsigned* list = (unsigned*)(at + 256 + counter_bytes + base_bytes);
+    float4* base_px = (float4*)(at + 256);
+    unsigned* list = (unsigned*)(at + 256 + base_bytes);
     if (!ds.adaptive_count_host) {
         if (hipError_t e = hipHostMalloc((void**)&ds.adaptive_count_host, sizeof(unsigned long long), hipHostMallocDefault);
             e != hipSuccess)
@@ -198,7 +139,7 @@ hipError_t launch_render_adaptive(device_scene& ds, const dev_render_args& args,
     if (hipError_t e = hipMemsetAsync(count, 0, sizeof(unsigned long long), stream); e != hipSuccess) return e;
     if (hipError_t e = launch_render_wavefront(ds, base, base_px, counters, false, packet, stream); e != hipSuccess)
         return e;
-    int t = T.begin(phase_lists, stream);
+    const int t = T.begin(phase_lists, stream);
     hipLaunchKernelGGL(k_adaptive_flag,
                        dim3((args.tile_w + AD_BLOCK_X - 1) / AD_BLOCK_X, (args.tile_h + AD_BLOCK_Y - 1) / AD_BLOCK_Y),
                        dim3(AD_BLOCK_X, AD_BLOCK_Y), 0, stream, args, adaptive_base{base_px, base.x0, base.y0, base.tile_w},
@@ -214,39 +155,12 @@ hipError_t launch_render_adaptive(device_scene& ds, const dev_render_args& args,
     ds.adaptive_refined = (unsigned long long)flagged;
     if (flagged == 0) return hipSuccess;
 
-    // whole pixels per chunk: the caller's, or what keeps rays + colours within the budget
-    // (adaptive_chunk_rays; a batch's rays are counted in an int)
-    const long long budget = chunk_pixels > 0 ? chunk_pixels : std::max<long long>(1, adaptive_chunk_rays / spp);
-    const int per_chunk = (int)std::min({flagged, budget, std::max<long long>(1, (1ll << 30) / spp)});
-    const size_t ray_bytes = adaptive_align((size_t)per_chunk * spp * 2 * sizeof(float4));
-    if (hipError_t e = grow(ds.adaptive_rays, ds.adaptive_rays_bytes, ray_bytes + (size_t)per_chunk * spp * sizeof(float4));
-        e != hipSuccess)
-        return e;
-    float4* rays = (float4*)ds.adaptive_rays;
-    float4* colours = (float4*)((char*)ds.adaptive_rays + ray_bytes);
+    // the listed pixels at the call's samples, added to the counters the base render started;
     // what the base render reported of its lists and staging stays the call's report
     const bool camera_lists = ds.last_camera_lists, bundles = ds.last_bundles;
     const int staged = ds.last_lds_staging;
-    hipError_t e = hipSuccess;
-    for (long long k0 = 0; k0 < flagged && e == hipSuccess; k0 += per_chunk) {
-        const int npix = (int)std::min<long long>(per_chunk, flagged - k0);
-        const int n = npix * spp;
-        t = T.begin(phase_primary, stream);
-        hipLaunchKernelGGL(k_adaptive_rays, dim3((n + AD_BLOCK - 1) / AD_BLOCK), dim3(AD_BLOCK), 0, stream, args, list + k0,
-                           npix, rays);
-        T.end(t, stream);
-        e = hipMemcpyAsync(saved, counters, counter_bytes, hipMemcpyDeviceToDevice, stream);
-        if (e == hipSuccess)
-            e = launch_shade_rays_wavefront(ds, args, (const float*)rays, n, colours, counters, packet, stream);
-        if (e != hipSuccess) break;
-        t = T.begin(phase_accumulate, stream);
-        hipLaunchKernelGGL(k_adaptive_add_counters, dim3((cnt_slots * cnt_count + AD_BLOCK - 1) / AD_BLOCK), dim3(AD_BLOCK),
-                           0, stream, counters, saved);
-        hipLaunchKernelGGL(k_adaptive_resolve, dim3((npix + AD_BLOCK - 1) / AD_BLOCK), dim3(AD_BLOCK), 0, stream, args,
-                           list + k0, npix, colours, (float4*)out_rgba);
-        T.end(t, stream);
-        e = hipGetLastError();
-    }
+    const hipError_t e = render_pixel_batches(ds, args, camera_perspective, 0.0f, list, flagged, chunk_pixels, nullptr,
+                                              (float4*)out_rgba, counters, true, packet, stream);
     ds.last_camera_lists = camera_lists, ds.last_bundles = bundles;
     ds.last_lds_staging = staged;
     return e;

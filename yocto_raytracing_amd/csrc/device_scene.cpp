@@ -901,7 +901,7 @@ void device_scene_destroy(device_scene* ds) {
     if (ds->list_stats_ev) (void)hipEventDestroy(ds->list_stats_ev);
     if (ds->list_stats_host) (void)hipHostFree(ds->list_stats_host);
     if (ds->adaptive_frame) (void)hipFree(ds->adaptive_frame);
-    if (ds->adaptive_rays) (void)hipFree(ds->adaptive_rays);
+    if (ds->batch_rays) (void)hipFree(ds->batch_rays);
     if (ds->soft_radius) (void)hipFree(ds->soft_radius);
     if (ds->adaptive_count_ev) (void)hipEventDestroy(ds->adaptive_count_ev);
     if (ds->adaptive_count_host) (void)hipHostFree(ds->adaptive_count_host);

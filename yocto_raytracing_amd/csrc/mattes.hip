@@ -3,9 +3,10 @@
 // samples, ranked by that share (the Cryptomatte form). A pass of its own beside yrt_render
 // and yrt_render_aovs, on the beauty's sample grid (raytrace(), src/raytrace.cpp:228-250).
 // render.hip includes this file after aov.hip: the pass is a part of that translation unit
-// and of its gfx950 code object, and uses aov.hip's tile geometry.
+// and of its gfx950 code object, and runs on aov.hip's tile frame (tile_pixel_of,
+// tile_camera_sample, tile_count_camera_samples, hit_ids_of, tile_grid).
 //
-// k_aov's geometry: one lane owns one pixel, a wave an 8 x 8 tile walked together by
+// The tile passes' geometry: one lane owns one pixel, a wave an 8 x 8 tile walked together by
 // packet_first, the lane loops over the s*s sub-samples in the reference's order. Every
 // requested key is served by the one walk: the keys differ only in which integer of the hit's
 // instance record is counted.
@@ -109,45 +110,27 @@ __global__ __launch_bounds__(AOV_BLOCK) void k_matte(dev_scene_view S, dev_rende
                                                      matte_out<LAYERS, NKEYS> O, unsigned long long* dropped,
                                                      unsigned long long* counters) {
     constexpr int R = 4 * LAYERS;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int lx = (blockIdx.x * AOV_BLOCK_TILES + (wave % AOV_BLOCK_TILES)) * AOV_TILE + (lane % AOV_TILE);
-    const int ly = (blockIdx.y * AOV_BLOCK_TILES + (wave / AOV_BLOCK_TILES)) * AOV_TILE + (lane / AOV_TILE);
-    const bool in_window = lx < A.tile_w && ly < A.tile_h;
-    // this lane's image row under the band interleave, as in k_aov
-    const int i = A.x0 + lx;
-    const int b = ly / A.band, r = ly % A.band;
-    const int j = A.y0 + (b * A.band_stride + A.band_offset) * A.band + r;
     // local rows past the image edge read as empty tables: id -1, coverage 0
-    const bool valid = in_window && i < A.width && j < A.height;
-    if (!__ballot(in_window)) return;  // a tile outside the window: nothing to trace or write
+    const tile_pixel P = tile_pixel_of(A);
+    if (!__ballot(P.in_window)) return;  // a tile outside the window: nothing to trace or write
 
     const int ns = A.samples;
     matte_table<R> tab[NKEYS];
     int drops[NKEYS];
 #pragma unroll
     for (int k = 0; k < NKEYS; k++) matte_clear(tab[k]), drops[k] = 0;
-    if (__ballot(valid)) {
+    if (__ballot(P.valid)) {
         for (int jj = 0; jj < ns; jj++) {
             for (int ii = 0; ii < ns; ii++) {
-                // every lane reaches the walk; lanes without a pixel pass valid = false
-                ray3 ray = {{0, 0, 0}, {0, 0, 1}, 0, 0};
-                if (valid) ray = camera_ray(A.cam, A.width, A.height, ns, i, j, ii, jj);
-                hit_record hr = {-1, -1, {0, 0, 0, 0}, 0};
                 work_counts wc;
-                const bool h = packet_first<false>(S, ray, valid, hr, wc);
-                const bool hit = valid && h;
-                // the ids of YRT_AOV_IDS (k_aov): instance in scene order, material, shape
-                int id_inst = -1, id_mat = -1, id_shape = -1;
-                if (hit) {
-                    const f4* ti = S.tinst + 4 * hr.slot;
-                    id_inst = S.tinst_id[hr.slot];
-                    id_mat = (int)((uint32_t)ibits(ti[2].w) & mat_index_mask);
-                    id_shape = ibits(ti[0].w) & (int)inst_shape_mask;
-                }
+                const tile_sample cs = tile_camera_sample(S, A, P, ii, jj, wc);
+                const bool hit = P.valid && cs.hit;
+                hit_ids ids = {-1, -1, -1};
+                if (hit) ids = hit_ids_of(S, cs.hr);
 #pragma unroll
                 for (int k = 0; k < NKEYS; k++) {
                     const unsigned key = keys >> (2 * k) & 3u;
-                    const int v = key == matte_instance ? id_inst : key == matte_material ? id_mat : id_shape;
+                    const int v = key == matte_instance ? ids.inst : key == matte_material ? ids.mat : ids.shape;
                     drops[k] += matte_add(tab[k], v, hit) ? 0 : 1;
                 }
             }
@@ -157,8 +140,8 @@ __global__ __launch_bounds__(AOV_BLOCK) void k_matte(dev_scene_view S, dev_rende
 #pragma unroll
     for (int k = 0; k < NKEYS; k++) {
         matte_sort(tab[k]);
-        if (in_window) {
-            const size_t at = (size_t)ly * A.out_stride + lx;
+        if (P.in_window) {
+            const size_t at = P.at(A);
 #pragma unroll
             for (int l = 0; l < LAYERS; l++) {
                 O.ids[k][l][at] = make_int4(tab[k].id[4 * l], tab[k].id[4 * l + 1], tab[k].id[4 * l + 2], tab[k].id[4 * l + 3]);
@@ -168,12 +151,9 @@ __global__ __launch_bounds__(AOV_BLOCK) void k_matte(dev_scene_view S, dev_rende
         }
         // the key's dropped samples: one wave sum, at most one atomic per wave and key
         const unsigned long long dk = wave_sum((unsigned long long)drops[k]);
-        if (lane == 0 && dk) atomicAdd(matte_drop_line(dropped) + (keys >> (2 * k) & 3u), dk);
+        if (P.lane == 0 && dk) atomicAdd(matte_drop_line(dropped) + (keys >> (2 * k) & 3u), dk);
     }
-    // rays == camera samples, counted as in k_aov
-    static_assert(cnt_rays == 0 && cnt_samples == 1, "lanes 0 and 1 add to the line's first two counters");
-    const unsigned long long s = wave_sum(valid ? (unsigned long long)(ns * ns) : 0ull);
-    if (lane < 2 && s) atomicAdd(counter_line(counters) + lane, s);
+    tile_count_camera_samples(counters, P, ns);
 }
 
 template <int LAYERS, int NKEYS>
@@ -192,9 +172,7 @@ hipError_t launch_mattes_as(const device_scene& ds, const dev_render_args& args,
         }
         k++;
     }
-    constexpr int side = AOV_TILE * AOV_BLOCK_TILES;
-    dim3 grid((args.tile_w + side - 1) / side, (args.tile_h + side - 1) / side);
-    hipLaunchKernelGGL((k_matte<LAYERS, NKEYS>), grid, dim3(AOV_BLOCK), 0, stream, ds.view, args, keys, o, dropped,
+    hipLaunchKernelGGL((k_matte<LAYERS, NKEYS>), tile_grid(args), dim3(AOV_BLOCK), 0, stream, ds.view, args, keys, o, dropped,
                        counters);
     return hipGetLastError();
 }

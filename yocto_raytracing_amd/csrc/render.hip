@@ -379,13 +379,17 @@ hipError_t launch_tonemap(const float* rgba, int n, unsigned char* out, const to
 
 }  // namespace yrt
 
-// the AOV pass (k_aov, launch_aovs): a file of its own in this translation unit
+// The features below are files of their own in this translation unit (one gfx950 code object
+// per entry of build.py's SOURCES), included in the order of what each takes from the earlier:
+// the AOV pass (k_aov, launch_aovs) and the tile passes' frame: a lane's pixel, the camera
+// sample, the sample count, a hit's ids and the launch grid
 #include "aov.hip"
-// the ID-matte pass (k_matte, launch_mattes), on the AOV pass's tile geometry
+// the ID-matte pass (k_matte, launch_mattes), on aov.hip's tile frame
 #include "mattes.hip"
-// adaptive supersampling (k_adaptive_*, launch_render_adaptive)
-#include "adaptive.hip"
-// ambient occlusion (k_ao, launch_ao), on the AOV pass's tile geometry
+// ambient occlusion (k_ao, launch_ao), on aov.hip's tile frame; defines the tables ao_dirs, ao_rots
 #include "ao.hip"
-// camera models (k_camera_rays, k_camera_resolve, launch_render_camera), on adaptive.hip's batches
+// camera models (k_camera_rays, k_camera_resolve, launch_render_camera) and the pixel-batch
+// pipeline (render_pixel_batches); the lens samples are ao.hip's tables
 #include "camera.hip"
+// adaptive supersampling (k_adaptive_flag, launch_render_adaptive), on camera.hip's pixel batches
+#include "adaptive.hip"

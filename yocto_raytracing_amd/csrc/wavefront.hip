@@ -3599,10 +3599,12 @@ hipError_t run(device_scene& ds, const dev_render_args& A, float4* out, unsigned
 // handle reports neither as used. The mirror levels, the fold and the workspace are run()'s;
 // the fold's last step writes the ray's colour straight into `out` (B.rad), in batch order.
 // soft (yrt_shade_rays_soft): every level's shadow rays are k_soft_shadow's K rays per light and
-// its shading k_soft_shade's; null: yrt_shade_rays
+// its shading k_soft_shade's; null: yrt_shade_rays. keep_counters: no chunk is the call's first,
+// so the batch's counts add to what the counter lines hold (a pixel-batch render's later batches)
 template <bool PACKET, typename SE>
 hipError_t run_rays(device_scene& ds, const dev_render_args& A, const float* rays, int n, float4* out,
-                    unsigned long long* counters, hipStream_t stream, const soft_shadow_args* soft = nullptr) {
+                    unsigned long long* counters, hipStream_t stream, const soft_shadow_args* soft = nullptr,
+                    bool keep_counters = false) {
     chunk_plan plan;
     if (hipError_t e = plan_chunks(ds, A, n, 1, 1, nullptr, nullptr, plan); e != hipSuccess) return e;
     wf_buffers& B = plan.B;
@@ -3617,7 +3619,8 @@ hipError_t run_rays(device_scene& ds, const dev_render_args& A, const float* ray
         B.rays = rays + (size_t)r0 * 8;
         B.rad = reinterpret_cast<f4*>(out + r0);
         int t = T.begin(phase_lists, stream);
-        launch_chunk_setup(ds, B, 0, cam4, nullptr, plan.nlevels, counters, r0 == 0, stream);  // (no camera-relative records)
+        // (no camera-relative records)
+        launch_chunk_setup(ds, B, 0, cam4, nullptr, plan.nlevels, counters, r0 == 0 && !keep_counters, stream);
         T.end(t, stream);
         t = T.begin(phase_primary, stream);
         hipLaunchKernelGGL((k_rays_first<PACKET, SE>), dim3((nsamp + WF_BLOCK - 1) / WF_BLOCK), dim3(WF_BLOCK), 0,
@@ -3659,13 +3662,13 @@ hipError_t run_rays(device_scene& ds, const dev_render_args& A, const float* ray
 
 hipError_t launch_shade_rays_wavefront(device_scene& ds, const dev_render_args& args, const float* rays, int n,
                                        void* out_rgba, unsigned long long* counters, bool packet, hipStream_t stream,
-                                       const soft_shadow_args* soft) {
-    if (n <= 0) return clear_counters(counters, stream);  // (no chunk)
+                                       const soft_shadow_args* soft, bool keep_counters) {
+    if (n <= 0) return keep_counters ? hipSuccess : clear_counters(counters, stream);  // (no chunk)
     if (soft && (soft->rays < 1 || soft->rays > soft_shadow_rays_max || (ds.nlights > 0 && !soft->radius)))
         return hipErrorInvalidValue;
     return with_walk(ds, packet, [&](auto pk, auto se) {
         return run_rays<decltype(pk)::value, decltype(se)>(ds, args, rays, n, (float4*)out_rgba, counters, stream,
-                                                           soft);
+                                                           soft, keep_counters);
     });
 }
 

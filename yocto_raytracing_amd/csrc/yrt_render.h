@@ -85,14 +85,16 @@ struct device_scene {
     // yrt_render_light_groups: the last call's table of lights sorted by plane, the source of
     // its copy to the device (wavefront.hip group_buffers::tab)
     std::vector<int> group_tab;
-    // yrt_render_adaptive (adaptive.hip), grown on demand like `work`: the frame scratch (the
-    // flagged count, the saved counter lines, the base frame with its apron, the flagged list)
-    // and a chunk's rays and colours; the flagged count on the host (pinned), copied back
-    // behind the flag kernel, and the last call's value of it
+    // the pixel-batch renders (camera.hip render_pixel_batches: yrt_render_adaptive,
+    // yrt_render_camera, yrt_render_soft_shadows), grown on demand like `work`: a chunk's rays
+    // and colours
+    void* batch_rays = nullptr;
+    size_t batch_rays_bytes = 0;
+    // yrt_render_adaptive (adaptive.hip), grown on demand too: the frame scratch (the flagged
+    // count, the base frame with its apron, the flagged list); the flagged count on the host
+    // (pinned), copied back behind the flag kernel, and the last call's value of it
     void* adaptive_frame = nullptr;
     size_t adaptive_frame_bytes = 0;
-    void* adaptive_rays = nullptr;
-    size_t adaptive_rays_bytes = 0;
     unsigned long long* adaptive_count_host = nullptr;
     hipEvent_t adaptive_count_ev = nullptr;
     unsigned long long adaptive_refined = 0;
@@ -188,6 +190,8 @@ hipError_t launch_render_wavefront(device_scene& ds, const dev_render_args& args
 // tmin, tmax} and out n x RGBA f32, both device pointers; args carries amb and max_depth only.
 // The wavefront pipeline in ray mode (wavefront.hip run_rays: k_rays_first as level 0, then the
 // render's levels; counters zeroed in its first kernel, timings per phase) ...
+// With keep_counters that kernel leaves the counter lines alone and the batch's counts add to
+// what they hold: a render made of several batches (camera.hip) passes it from its second on.
 // With `soft` (yrt_shade_rays_soft) every light is a disk: K = soft->rays any-hit rays per (hit
 // sample, light) at every level (k_soft_shadow), the light's term scaled by the unoccluded share
 // (k_soft_shade). soft->radius is device memory, a radius per light (upload_soft_shadow_radii).
@@ -198,7 +202,7 @@ struct soft_shadow_args {
 };
 hipError_t launch_shade_rays_wavefront(device_scene& ds, const dev_render_args& args, const float* rays, int n,
                                        void* out_rgba, unsigned long long* counters, bool packet, hipStream_t stream,
-                                       const soft_shadow_args* soft = nullptr);
+                                       const soft_shadow_args* soft = nullptr, bool keep_counters = false);
 // the call's radii into ds.soft_radius, in stream order: radius[nlights] (host), or `all` for
 // every light when radius is null
 hipError_t upload_soft_shadow_radii(device_scene& ds, const float* radius, float all, hipStream_t stream);
@@ -241,16 +245,23 @@ hipError_t launch_render_wavefront_light_groups(device_scene& ds, const dev_rend
                                                 int ngroups, const dev_light_group_planes& out,
                                                 unsigned long long* counters, bool packet, hipStream_t stream);
 
+// The pixel-batch renders (camera.hip render_pixel_batches) shade whole pixels as ray batches:
+// k_camera_rays generates a chunk of pixels' rays, launch_shade_rays_wavefront shades them,
+// k_camera_resolve sums each pixel's colours into the image, chunk_pixels pixels a batch (0: as
+// many as keep a chunk within pixel_batch_rays rays). A chunk's rays and colours live in
+// ds.batch_rays. The first batch of a call whose counters nothing has started zeroes them;
+// every other batch adds to them (keep_counters).
+constexpr long long pixel_batch_rays = 1ll << 23;  // 48 B a ray (32 B ray + 16 B colour): 384 MiB
+
 // adaptive supersampling (adaptive.hip, yrt_render_adaptive): args is the call's frame at its
 // full samples per axis (contiguous rows: band 1, stride 1, offset 0). The base frame at
 // base_samples per axis comes from launch_render_wavefront over the window grown by one pixel
 // (into scratch), k_adaptive_flag tests it against `threshold`, writes it to out_rgba, the byte
 // mask to `refined` (may be null; out's layout, 1 B per pixel) and the flagged pixels to a list,
-// and the flagged pixels are refined in chunks of chunk_pixels (0: as many as keep a chunk within
-// adaptive_chunk_rays rays) through launch_shade_rays_wavefront. Waits once on the stream, for
-// the flagged count (kept in ds.adaptive_refined). The counters are the base render's plus the
-// batches'; timings are added per phase.
-constexpr long long adaptive_chunk_rays = 1ll << 23;  // 48 B a ray (32 B ray + 16 B colour): 384 MiB
+// and the listed pixels are refined as pixel batches of the pinhole (camera_perspective at
+// aperture 0: camera_ray's bits). Waits once on the stream, for the flagged count (kept in
+// ds.adaptive_refined). The base render starts the counters and every batch adds to them;
+// timings are added per phase.
 hipError_t launch_render_adaptive(device_scene& ds, const dev_render_args& args, int base_samples, float threshold,
                                   int chunk_pixels, void* out_rgba, unsigned char* refined,
                                   unsigned long long* counters, bool packet, hipStream_t stream);
@@ -258,12 +269,9 @@ hipError_t launch_render_adaptive(device_scene& ds, const dev_render_args& args,
 // camera models (camera.hip, yrt_render_camera / yrt_camera_rays): `model` is a camera_model of
 // camera_models.h and `aperture` the resolved lens diameter (camera_args.h); args is the call's
 // frame with the call's focus in args.cam (contiguous rows: band 1, stride 1, offset 0).
-// launch_render_camera writes the window's image: k_camera_rays generates a chunk of whole
-// pixels' rays, launch_shade_rays_wavefront shades them, k_camera_resolve sums each pixel's
-// colours into out_rgba, chunk_pixels pixels a batch (0: as many as keep a chunk within
-// adaptive_chunk_rays rays). The chunks' rays and colours live in ds.adaptive_rays and the saved
-// counter lines in ds.adaptive_frame. The counters are the batches' sums; timings are added per
-// phase; the handle reports no lists and no staging afterwards.
+// launch_render_camera writes the window's image as pixel batches over the window's pixels in
+// row-major order. The counters are the batches' sums; timings are added per phase; the handle
+// reports no lists and no staging afterwards.
 hipError_t launch_render_camera(device_scene& ds, const dev_render_args& args, int model, float aperture,
                                 int chunk_pixels, void* out_rgba, unsigned long long* counters, bool packet,
                                 hipStream_t stream);
